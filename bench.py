@@ -23,6 +23,11 @@ fields the line carries
                    of the fused KernelConv -> FAC kernel (N=1 only)
   cpu_baseline     the CPU oracle (oracle/model_ref.py + loss_ref.py, a port of the reference path) timed on this box's
                    host cores on a bounded sample (rank 0, N=1 only)
+
+--dump-outputs DIR writes what the LAST timed step computed (rank 0): DIR/loss.npy (the loss train_step returned),
+DIR/grad.npy (the packed, rank-averaged gradient the optimiser consumed) and DIR/params.npy (the flat parameter buffer after
+the update), all float32, 45.5 MB in all.  Weights and batch are seeded, so with the same arguments every run starts from
+the same inputs and two builds can be compared array for array.
 """
 import argparse
 import json
@@ -417,6 +422,26 @@ def write_detail(full, path):
     return written
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(arrays, out_dir):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (float64 stays float64); at most DUMP_LIMIT_BYTES in
+    all.  Returns {name: path}."""
+    import numpy as np
+    arrays = {name: np.asarray(a) for name, a in arrays.items()}
+    arrays = {name: (a if a.dtype == np.float64 else a.astype(np.float32)) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    paths = {}
+    for name, a in arrays.items():
+        paths[name] = os.path.join(out_dir, name + ".npy")
+        np.save(paths[name], a)
+    return paths
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher's environment: run
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same flags>`
@@ -460,7 +485,12 @@ def main():
                          "stdout carries the contract fields, roofline and cpu_baseline only (< 4 KB)")
     ap.add_argument("--no-bf16-leg", "--no-extra-legs", dest="no_extra_legs", action="store_true",
                     help="skip the secondary measurement of the same step in the exact-fp32 mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): loss, "
+                         "packed gradient, updated parameters")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves, as a CHILD process (never an exec), before anything
@@ -537,6 +567,11 @@ def main():
         if dist.is_initialized():
             dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
         note("%s timed region: %d steps in %.3f s (max over ranks %.3f s)" % (tag, args.steps, elapsed, t_max.item()))
+        if args.dump_outputs and rank == 0 and tag == args.precision:
+            # (copied before the profiled pass below takes further steps)
+            paths = write_outputs({"loss": loss.detach().cpu(), "grad": eng.bucket.flat.detach().cpu(),
+                                   "params": eng.optimizer.flat.detach().cpu()}, args.dump_outputs)
+            note("outputs of the last timed step: %s" % ", ".join(sorted(paths.values())))
         loss_value = float(loss.item())
         graph_mode, eng.use_graph = eng.use_graph, False
         eng.train_step(*batch)                      # eager path warm (allocator) before the profiled pass

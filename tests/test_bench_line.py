@@ -80,3 +80,20 @@ def test_detail_file_holds_the_full_record(tmp_path, capsys):
     assert json.load(open(path))["kernels"].keys() == full["kernels"].keys()
     err = capsys.readouterr().err
     assert all(not ln.startswith("{") for ln in err.splitlines())      # nothing on stderr looks like the bench's JSON line
+
+
+def test_dump_outputs_writes_float32_npy_under_the_limit(tmp_path):
+    import numpy as np
+    import pytest
+    import torch
+    paths = bench.write_outputs({"loss": torch.tensor(3.5), "grad": torch.arange(6, dtype=torch.float16),
+                                 "params": np.linspace(0, 1, 5)}, str(tmp_path / "out"))
+    assert sorted(paths) == ["grad", "loss", "params"]
+    assert all(p == str(tmp_path / "out" / (n + ".npy")) for n, p in paths.items())
+    loss, grad, params = (np.load(paths[n]) for n in ("loss", "grad", "params"))
+    assert loss.dtype == np.float32 and loss.shape == () and loss == 3.5
+    assert grad.dtype == np.float32 and np.array_equal(grad, np.arange(6, dtype=np.float32))
+    assert params.dtype == np.float64 and np.array_equal(params, np.linspace(0, 1, 5))
+    with pytest.raises(ValueError):
+        bench.write_outputs({"big": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)}, str(tmp_path / "big"))
+    assert not (tmp_path / "big").exists()

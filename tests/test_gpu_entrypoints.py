@@ -143,6 +143,36 @@ def test_bench_form_stays_native_under_strict(tmp_path):
     assert full["fp32_exact_mode"]["ms_per_step"] > d["ms_per_step"]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's loss, packed gradient and updated parameters as float32 .npy files (< 64 MB);
+    `--steps` is the number of timed steps; two runs with the same arguments start from the same inputs, and the step is
+    bit-reproducible (tests/test_gpu_model.py::test_training_step_is_bit_reproducible), so their outputs are identical."""
+    import json
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "EBFI_BENCH_REHEARSAL", "EBFI_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    runs = []
+    for i in range(2):
+        out = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--no-extra-legs", "--no-ops", "--no-inference", "--no-cpu-baseline", "--detail",
+                            str(tmp_path / ("detail%d.json" % i)), "--dump-outputs", str(out)],
+                           capture_output=True, text=True, env=env, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == ["grad.npy", "loss.npy", "params.npy"]
+        arrays = {n: np.load(str(out / (n + ".npy"))) for n in ("loss", "grad", "params")}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["grad"].shape == arrays["params"].shape and arrays["grad"].size > 5e6 and np.abs(arrays["grad"]).sum() > 0
+        assert float(arrays["loss"]) == d["config"]["loss"]
+        runs.append(arrays)
+    for n in ("loss", "grad", "params"):
+        np.testing.assert_array_equal(runs[0][n], runs[1][n], err_msg=n)
+
+
 def test_bench_single_rank_over_rccl():
     """What a one-GPU box can exercise of the RCCL path: bench.py as ONE rank with the process group initialised on backend
     'nccl' (= RCCL), its watchdog thread alive during the hipGraph capture (strict), and the step's collective -- the
