@@ -2,16 +2,20 @@
 """Headline benchmark: interpolated frames/s of the EVFIAutoEx training step (forward + Lap/census
 loss + backward + flat RCCL gradient all-reduce + Adam) at B=8 per GPU, 256x256, synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: starts its N ranks itself, as a child process)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: starts its N ranks itself, as a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
 
 One process per GPU; weak scaling (B=8 per rank); ONE collective per step (the flat gradient buffer with the fp16 overflow
 flag as its last element).  Rank 0 prints ONE JSON line.  For N > 1 a failed hipGraph capture is an error (--strict-graph is
 the default there).  Default precision: bf16x3
 (split-precision conv operands, fp32-grade accuracy, parity-tested at 1e-3 like the exact fp32 mode); forward + loss +
-backward + gradient packing are replayed from one captured hipGraph (--no-graph launches eagerly).  Besides the contract
-fields the line carries
+backward + gradient packing are replayed from one captured hipGraph (--no-graph launches eagerly).
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, --dump-outputs, the replica
+check (parameter checksums compared across ranks) and the line.  Its `roofline` and `cpu_baseline` are null, and no detail
+file is written.  With --full the run goes on after the timed steps and records the following (summaries on the line,
+everything in the --detail file; the --no-* options skip parts):
   roofline         the dominant hand-written kernel of the step by device time: its bound (matrix cores or HBM, whichever
                    floor is higher for the work it was given), achieved vs peak, PMC traffic per launch; measured with
                    hipEvent pairs the library records on the launch stream during a second, eager pass of the same K steps
@@ -360,7 +364,8 @@ LINE_LIMIT = 4096          # the driver parses ONE JSON line from stdout; round 
 def compact_line(full, detail_path=None):
     """The ONE line rank 0 prints: the contract fields, a short `config`, the dominant kernel's `roofline`, `cpu_baseline`, the
     north_star op figure and three inference scalars -- under LINE_LIMIT bytes whatever the per-kernel tables hold.  Everything
-    else (every kernel of both legs, the op block, the inference block) goes to `bench_detail.json` and to stderr."""
+    else (every kernel of both legs, the op block, the inference block) goes to `bench_detail.json` and to stderr.  Without
+    --full only the contract fields and `config` carry values (`roofline` and `cpu_baseline` are null)."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data")
     line = {k: full.get(k) for k in keep}
@@ -472,19 +477,23 @@ def main():
                          "(default; parity-checked at 1e-3 like fp32); fp32 = exact fp32 matrix cores; bf16 = single rounding")
     ap.add_argument("--no-graph", action="store_true",
                     help="launch every kernel of the step eagerly instead of replaying the captured hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ops", action="store_true", help="skip the FAC / DCNv2 op block (north_star target figure)")
-    ap.add_argument("--no-inference", action="store_true", help="skip the inference block (BASELINE configs 2 and 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the per-kernel table and roofline "
+                         "(a profiled eager pass), the exact-fp32 leg, the op block, the inference block and the CPU baseline; "
+                         "writes the detail file")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ops", action="store_true", help="with --full: skip the FAC / DCNv2 op block (north_star target figure)")
+    ap.add_argument("--no-inference", action="store_true", help="with --full: skip the inference block (BASELINE configs 2 and 5)")
     ap.add_argument("--strict-graph", dest="strict_graph", action="store_true", default=None,
                     help="exit non-zero when the hipGraph capture of the step failed and the engine fell back to eager launches "
                          "(default for --gpus > 1: one rank silently 20 %% slower would drag every rank; with one GPU the default "
                          "is to report it as config.graph_capture_failed and in config.launch)")
     ap.add_argument("--no-strict-graph", dest="strict_graph", action="store_false")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
-                    help="where the full record goes (per-kernel tables of both legs, op block, inference block); the ONE line on "
-                         "stdout carries the contract fields, roofline and cpu_baseline only (< 4 KB)")
+                    help="with --full: where the full record goes (per-kernel tables of both legs, op block, inference block); "
+                         "the ONE line on stdout carries the contract fields, roofline and cpu_baseline only (< 4 KB)")
     ap.add_argument("--no-bf16-leg", "--no-extra-legs", dest="no_extra_legs", action="store_true",
-                    help="skip the secondary measurement of the same step in the exact-fp32 mode")
+                    help="with --full: skip the secondary measurement of the same step in the exact-fp32 mode")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): loss, "
                          "packed gradient, updated parameters")
@@ -541,9 +550,9 @@ def main():
 
     def timed_run(tag):
         """W untimed warm-up steps, then EXACTLY K timed steps between barrier + synchronize (max over ranks);
-        afterwards the same K steps once more, eagerly, with the library's hipEvent pairs switched on, for the
-        per-kernel table (a hipGraph replay cannot carry per-kernel event pairs, and the pairs cost a little time,
-        so they stay out of the timed region)."""
+        with --full, afterwards the same K steps once more, eagerly, with the library's hipEvent pairs switched on,
+        for the per-kernel table (a hipGraph replay cannot carry per-kernel event pairs, and the pairs cost a little
+        time, so they stay out of the timed region)."""
         # the engine's first steps are not the steady state: with the fp16 backward it takes `calibration_steps` eager steps
         # (operand scales measured just in time) and captures the graph on the next one.  If W is too small to cover
         # them, extra untimed steps are added so that the timed region never holds a capture (reported as untimed_steps).
@@ -573,6 +582,8 @@ def main():
                                    "params": eng.optimizer.flat.detach().cpu()}, args.dump_outputs)
             note("outputs of the last timed step: %s" % ", ".join(sorted(paths.values())))
         loss_value = float(loss.item())
+        if not args.full:
+            return t_max.item(), None, loss_value, None
         graph_mode, eng.use_graph = eng.use_graph, False
         eng.train_step(*batch)                      # eager path warm (allocator) before the profiled pass
         sync()
@@ -594,7 +605,7 @@ def main():
     note("engine + batch ready on %s (rank %d/%d)" % (device, rank, world))
     elapsed, kernels, loss, prof_elapsed = timed_run(args.precision)
     extra_leg = None
-    if args.precision == "bf16x3" and not args.no_extra_legs:
+    if args.full and args.precision == "bf16x3" and not args.no_extra_legs:
         eng.precision = "fp32"
         e2, k2, l2, pe2 = timed_run("fp32-leg")
         eng.precision = args.precision
@@ -628,7 +639,7 @@ def main():
         note("WARNING: hipGraph capture failed (%s): the timed region ran eager launches" % (capture_err or "on another rank"))
 
     if rank == 0:
-        per_kernel, roofline = kernel_table(kernels, prof_elapsed, args.steps)
+        per_kernel, roofline = kernel_table(kernels, prof_elapsed, args.steps) if args.full else ({}, None)
         if roofline is not None:
             roofline["measured"] = ("hipEvent pairs around every launch of the kernel during a second, eager pass of the same "
                                     "%d steps right after the timed region (%.3f ms/step with the pairs on)"
@@ -674,22 +685,22 @@ def main():
             "kernels": per_kernel,
             "fp32_exact_mode": extra_leg,
         }
-        if world == 1 and not args.no_ops:
+        if args.full and world == 1 and not args.no_ops:
             note("op block: FAC / DCNv2 at B=8, 128x128 features ...")
             del eng
             torch.cuda.empty_cache()
             out["ops"] = ops_block(device)
             out["dcn_fac_forward_frac_hbm"] = out["ops"]["dcn_fac_forward"]["frac_hbm"]
-        if world == 1 and not args.no_inference:
+        if args.full and world == 1 and not args.no_inference:
             note("inference block: configs 2 (B=4 256x256) and 5 (B=8 720x1280) ...")
             out["inference"] = inference_block(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             note("cpu baseline (oracle on host cores) ...")
             out["cpu_baseline"] = cpu_baseline(dict(DEFAULT_MODEL_ARGS))
             note("cpu baseline done")
         else:
             out["cpu_baseline"] = None
-        detail_path = write_detail(out, args.detail)
+        detail_path = write_detail(out, args.detail) if args.full else None
         print(compact_line(out, detail_path), flush=True)
     if dist.is_initialized():
         dist.barrier()

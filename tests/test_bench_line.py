@@ -73,6 +73,19 @@ def test_line_sheds_optional_parts_rather_than_overflow():
     assert len(json.dumps(d)) < 4096 and d["roofline"]["kernel"] == "conv_fwd_f16_ws" and d["cpu_baseline"]["value"] == 1.2336
 
 
+def test_plain_run_line_carries_the_contract_fields():
+    """The record of a run without --full (what main() builds then): no kernel table, legs or blocks, no detail file."""
+    full = full_record()
+    for k in ("ops", "dcn_fac_forward_frac_hbm", "inference"):
+        del full[k]
+    full.update(kernels={}, fp32_exact_mode=None, roofline=None, cpu_baseline=None)
+    d = json.loads(bench.compact_line(full, None))
+    assert d["value"] == 544.2 and d["ms_per_step"] == 14.7 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == full["dtype"] and d["metric"] == full["metric"] and d["config"]["untimed_steps"] == 5
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert not {"detail", "inference_frames_per_s", "fp32_exact_ms_per_step", "dcn_fac_forward_frac_hbm"} & set(d)
+
+
 def test_detail_file_holds_the_full_record(tmp_path, capsys):
     full = full_record()
     path = bench.write_detail(full, str(tmp_path / "bench_detail.json"))

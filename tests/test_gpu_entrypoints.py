@@ -49,13 +49,14 @@ def test_train_resume_infer(tmp_path):
 
 def test_bench_two_rank_rehearsal(tmp_path):
     """bench.py's multi-rank path (barrier, flat-bucket gradient all-reduce, max-over-ranks timing, rank-0 JSON)
-    rehearsed with 2 ranks sharing the one GPU over gloo (EBFI_BENCH_REHEARSAL=1); the real N>1 runs use RCCL."""
+    rehearsed with 2 ranks sharing the one GPU over gloo (EBFI_BENCH_REHEARSAL=1); the real N>1 runs use RCCL.  With --full:
+    the profiled pass and the detail file."""
     import json
     detail = str(tmp_path / "detail.json")
     env = dict(os.environ, EBFI_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29631", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-bf16-leg", "--detail", detail],
+                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-bf16-leg", "--detail", detail],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -120,8 +121,8 @@ def test_bench_plain_form_launches_its_own_ranks():
 
 
 def test_bench_form_stays_native_under_strict(tmp_path):
-    """The driver's bench form (`python bench.py --gpus 1 ...`: default widths, the split-precision leg with the fp16 backward, the
-    exact-fp32 leg, the three inference legs) with EBFI_STRICT_NATIVE=1: a convolution of the default model dispatched to torch /
+    """The full bench form (`python bench.py --gpus 1 ... --full`: default widths, the split-precision leg with the fp16 backward,
+    the exact-fp32 leg, the three inference legs) with EBFI_STRICT_NATIVE=1: a convolution of the default model dispatched to torch /
     MIOpen anywhere on these paths raises EbfiNativeError and fails the run (round 5: ResidualControl's scalar 1x1 convolutions
     still printed 'runs on torch' here).  Also what the driver needs from stdout: ONE line, < 4 KB, with roofline and config."""
     import json
@@ -129,8 +130,8 @@ def test_bench_form_stays_native_under_strict(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "EBFI_BENCH_REHEARSAL", "EBFI_BENCH_FORCE_DIST"):
         env.pop(k, None)
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-ops", "--detail", detail], capture_output=True, text=True, env=env, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
+                        "--no-cpu-baseline", "--no-ops", "--detail", detail], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "runs on torch" not in r.stderr
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -146,7 +147,8 @@ def test_bench_form_stays_native_under_strict(tmp_path):
 def test_bench_dump_outputs(tmp_path):
     """`--dump-outputs DIR`: the last timed step's loss, packed gradient and updated parameters as float32 .npy files (< 64 MB);
     `--steps` is the number of timed steps; two runs with the same arguments start from the same inputs, and the step is
-    bit-reproducible (tests/test_gpu_model.py::test_training_step_is_bit_reproducible), so their outputs are identical."""
+    bit-reproducible (tests/test_gpu_model.py::test_training_step_is_bit_reproducible), so their outputs are identical.  The first
+    run is the plain form (no profiled pass, no detail file), the second --full: the outputs are taken before what --full adds."""
     import json
     import numpy as np
     env = dict(os.environ)
@@ -155,13 +157,14 @@ def test_bench_dump_outputs(tmp_path):
     runs = []
     for i in range(2):
         out = tmp_path / ("out%d" % i)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                            "--no-extra-legs", "--no-ops", "--no-inference", "--no-cpu-baseline", "--detail",
-                            str(tmp_path / ("detail%d.json" % i)), "--dump-outputs", str(out)],
-                           capture_output=True, text=True, env=env, timeout=900)
+        detail = tmp_path / ("detail%d.json" % i)
+        full = ["--full", "--no-extra-legs", "--no-ops", "--no-inference", "--no-cpu-baseline"] if i else []
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"] + full +
+                           ["--detail", str(detail), "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
         assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert detail.exists() == bool(full) and (d["roofline"] is None) == (not full) and d["cpu_baseline"] is None
         assert sorted(os.listdir(out)) == ["grad.npy", "loss.npy", "params.npy"]
         arrays = {n: np.load(str(out / (n + ".npy"))) for n in ("loss", "grad", "params")}
         assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())

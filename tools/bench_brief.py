@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Prints the headline of a bench.py JSON line and its top kernels (development helper)."""
+"""Prints the headline of a `bench.py --full` detail file (--detail) and its top kernels (development helper)."""
 import json
 import sys
 d = json.load(open(sys.argv[1]))
