@@ -2470,14 +2470,12 @@ int pick_wtx_x3(int) { return 32; }
 // otherwise.  Measured (tools/kbench, 128x128, B=8): 64->64 54.5 vs 58.1 us, 128->64 87.1 vs 89.5, 64->128 85.9 vs 86.8,
 // 128->1600 1765 vs 1671 (the grad_out tile is fetched once per 32-channel block: with 25 output blocks that costs more
 // than the second resident workgroup hides).
-// wave-specialised form (conv_wgrad_x3_ws): every 3x3 layer; EBFI_WGRAD_WS=0 restores the uniform-wave kernels (A/B runs)
+// wave-specialised form (conv_wgrad_x3_ws): every 3x3 layer with 64-channel input blocks
 bool wgrad_x3_ws(const ConvGeom &g, int ks) {   // 64-channel input blocks: layers with other channel counts keep the 32-channel form
-    const char *e = dev_getenv("EBFI_WGRAD_WS");
-    return ks == 3 && g.Cin % 64 == 0 && !(e && e[0] == '0');
+    return ks == 3 && g.Cin % 64 == 0;
 }
 bool wgrad_x3_small_wg(const ConvGeom &g, int ks) {
-    const bool off = dev_getenv("EBFI_WGRAD_BIGWG") != nullptr;            // development switch (A/B runs)
-    return !off && !wgrad_x3_ws(g, ks) && ks == 3 && g.Cin % 32 == 0 && g.Cout <= 256;
+    return !wgrad_x3_ws(g, ks) && ks == 3 && g.Cin % 32 == 0 && g.Cout <= 256;
 }
 
 int wgrad_x3_splits(const ConvGeom &g, int ks) {
@@ -2858,8 +2856,7 @@ int launch_fwd_bf16(hipStream_t st, const float *x, const float *dact_y, const f
     // 32 output channels per workgroup when 64 would leave more than half of the CUs without one (small feature maps of the
     // detail branch): twice the workgroups, each with half the matrix work per staged chunk
     // (a requested fp16 side image pins the 64-channel wave-specialised form: its epilogue is the one that writes it)
-    const bool few = x3 && epi.out16 == nullptr && epi.post_scale == nullptr && g.store == 0 && tiles * ceil_div(g.Cout, 64) <= 128 &&
-                     dev_getenv("EBFI_CONV_NO_MT1") == nullptr;
+    const bool few = x3 && epi.out16 == nullptr && epi.post_scale == nullptr && g.store == 0 && tiles * ceil_div(g.Cout, 64) <= 128;
     const int mt = (g.Cout <= 32 || few) ? 1 : 2;
     dim3 grid((unsigned)tiles, (unsigned)ceil_div(g.Cout, 32 * mt));
     if (g.store != 0 && !x3) return fail(EBFI_ERR_UNSUPPORTED, "conv2d: shuffled output layouts are written by the split-precision kernels only");
@@ -2868,14 +2865,10 @@ int launch_fwd_bf16(hipStream_t st, const float *x, const float *dact_y, const f
         const size_t lds = (size_t)2 * (2 * PSX * 32 + 2 * KS * KS * 32 * mt * 32) + KB_LDS_BYTES;   // two buffers of unpadded hi/lo images
         // 16-byte input quads: rows must keep quads aligned, same-padding only; used where they pay (see the kernel's header)
         const bool vec4 = g.W % 4 == 0 && g.pad == KS / 2 && aligned16(x) && (!dact_y || aligned16(dact_y));
-        const char *ws_env = dev_getenv("EBFI_CONV_WS");
         const bool extra = epi.addend != nullptr || epi.mask_y != nullptr || epi.out16 != nullptr || epi.post_scale != nullptr;
         // wave-specialised form (conv_fwd_bf16x3_ws): every 3x3 layer the quad-staging producers can serve (64-channel blocks, no
-        // folded activation derivative); EBFI_CONV_WS=0 / 1 = never / only the long layers (development switch, A/B runs)
-        const bool ws_long = ceil_div(g.Cout, 64) >= 8 || K16 >= 512;
-        const bool ws_extra_ok = !extra || dev_getenv("EBFI_CONV_WS_NOEXTRA") == nullptr;
-        const bool use_ws = KS == 3 && mt == 2 && vec4 && dact == ACT_NONE && ws_extra_ok && !(ws_env && ws_env[0] == '0') &&
-                            (ws_long || !(ws_env && ws_env[0] == '1'));
+        // folded activation derivative)
+        const bool use_ws = KS == 3 && mt == 2 && vec4 && dact == ACT_NONE;
         if (epi.out16 != nullptr && !use_ws)
             return fail(EBFI_ERR_UNSUPPORTED, "conv2d: the fp16 side image is written by the wave-specialised 3x3 kernel only "
                         "(W %% 4 == 0, same padding, more than 32 output channels, 16-byte aligned input)");
@@ -2897,11 +2890,13 @@ int launch_fwd_bf16(hipStream_t st, const float *x, const float *dact_y, const f
     } while (0)
 #define EBFI_LAUNCH_X3(MT_, DA_)                                                                                          \
     do {                                                                                                                 \
-        if (vec == 4) EBFI_LAUNCH_X3V(MT_, DA_, 4);                                                                      \
-        else EBFI_LAUNCH_X3V(MT_, DA_, 1);                                                                               \
+        if constexpr (DA_ != ACT_NONE) {                                                                                 \
+            if (vec == 4) EBFI_LAUNCH_X3V(MT_, DA_, 4);                                                                  \
+            else EBFI_LAUNCH_X3V(MT_, DA_, 1);                                                                           \
+        } else EBFI_LAUNCH_X3V(MT_, DA_, 1);                                                                             \
     } while (0)
-        const char *vec_env = dev_getenv("EBFI_CONV_VEC");     // development switch (tools/kbench): 1 = dword loads, 4 = quad loads
-        const int vec = !vec4 ? 1 : (vec_env ? atoi(vec_env) : (dact != ACT_NONE ? 4 : 1));
+        // quad loads with a folded activation derivative only (see the kernel's header)
+        const int vec = vec4 && dact != ACT_NONE ? 4 : 1;
         // the persistent form (3x3, dword loads, no folded derivative): one round of workgroups, each walking
         // ceil(tiles / gx) pixel tiles of its output-channel block
         const int64_t co_blocks = ceil_div(g.Cout, 32 * mt);
@@ -2909,7 +2904,7 @@ int launch_fwd_bf16(hipStream_t st, const float *x, const float *dact_y, const f
         if (gx < 1) gx = 1;
         // (measured, round 4: rounding gx down to a multiple of 8 so that xcd_tile applies to the 128 -> 1600 layer -- 200 instead
         // of 250 workgroups -- is time-neutral: 1.23-1.27 ms against 1.15-1.34 ms; what the L2s save the idle CUs give back)
-        if (gx > tiles || dev_getenv("EBFI_CONV_NOPERSIST")) gx = tiles;
+        if (gx > tiles) gx = tiles;
         const dim3 pgrid((unsigned)gx, (unsigned)co_blocks);
         if constexpr (KS == 3) {
             if (use_ws) {
@@ -3341,7 +3336,7 @@ int conv_backward_data_bf16_impl(const char *who, int x3, const void *grad_outpu
     if (B == 0) return EBFI_OK;
     // the detail branch's output convolution (16 <- 3 channels on a full-resolution map): taps on the contraction axis of the thin
     // gradient (conv2d_shift.inc.hpp) instead of 49 taps of a 29/32-empty tile
-    if (k7 && Cout == 3 && Cin == 16 && (int64_t)B * H * W >= 64 * 1024 && dev_getenv("EBFI_NO_SHIFT_WGRAD") == nullptr)
+    if (k7 && Cout == 3 && Cin == 16 && (int64_t)B * H * W >= 64 * 1024)
         return launch_conv7_thin_dgrad(static_cast<hipStream_t>(stream), static_cast<const float *>(grad_output), nullptr,
                                        static_cast<const float *>(weight), static_cast<float *>(grad_input), B, H, W, f.Ho, f.Wo, pad,
                                        ACT_NONE, 0.f);
@@ -4026,14 +4021,12 @@ extern "C" int ebfi_conv2d_backward_weight_f16g_ex(const void *input, const void
     }
     int nsplit = wgrad_x3_splits(g, 3);
     // pre-activation gradients on quad-aligned rows: the pixel-major kernel with transposing LDS reads (conv_wgrad_f16_tr)
-    // (EBFI_WGRAD_TR=0 keeps the pair-word kernel for A/B runs.  A first in-step measurement had this kernel at 102 us against
+    // (the pair-word kernel serves the other layers.  A first in-step measurement had this kernel at 102 us against
     // 72 us on the 64 / 128-channel layers although it was faster in isolation; after the later changes of the round -- operand
     // scales and their running maxima on separate cache lines, channel blocks placed per XCD -- it runs 54-63 us inside the
     // step as well: 18.95 -> 18.45 ms per step with it on every eligible layer.)
-    const char *tr_env = dev_getenv("EBFI_WGRAD_TR");
     const int64_t tr_tiles = (int64_t)g.B * ceil_div(g.Ho, TRH) * ceil_div(g.Wo, TRW);
-    const bool tr_pays = !(tr_env && tr_env[0] == '0');
-    const bool tr_ok = pad == 1 && W % 4 == 0 && aligned16(input) && aligned16(grad_output) && tr_pays &&
+    const bool tr_ok = pad == 1 && W % 4 == 0 && aligned16(input) && aligned16(grad_output) &&
                        (act == ACT_NONE || aligned16(saved_output)) && (!grad_preact_out || aligned16(grad_preact_out));
     if (tr_ok) {
         const int64_t tiles = tr_tiles;

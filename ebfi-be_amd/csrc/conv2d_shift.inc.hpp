@@ -413,12 +413,9 @@ inline int shift_wgrad_slabs(const ConvGeom &g, const ShiftPlan &p) {
     return g.B * (int)ceil_div(Hu, SH_R) * (int)ceil_div(Wu, SH_W);
 }
 inline ShiftPlan shift_wgrad_plan(const ConvGeom &g, int ks, int stride, const void *x, const void *go, const void *y, const void *gp) {
-    ShiftPlan p = shift_wgrad_geometry(g, ks, stride);
-    if (p.kind == 0) return p;
     // (dwords everywhere except the optional 16-byte thick accesses, which check their own alignment: only fp32 alignment is required)
-    if (dev_getenv("EBFI_NO_SHIFT_WGRAD") != nullptr) p.kind = 0;
     (void)x; (void)go; (void)y; (void)gp;
-    return p;
+    return shift_wgrad_geometry(g, ks, stride);
 }
 
 template <int KS, int NT, bool THIN_OUT, int NCHR, bool ALIGNED, bool GPOUT>

@@ -327,8 +327,7 @@ inline ThinPlan thin_wgrad_plan(const ConvGeom &g, int ks, int stride, const voi
     ThinPlan p = thin_wgrad_geometry(g, ks, stride);
     if (p.kind == 0) return p;
     p.aligned = aligned16(x);
-    if (!aligned16(go) || (y && !aligned16(y)) || (gp && !aligned16(gp)) || !p.aligned || dev_getenv("EBFI_NO_THIN") != nullptr)
-        p.kind = 0;
+    if (!aligned16(go) || (y && !aligned16(y)) || (gp && !aligned16(gp)) || !p.aligned) p.kind = 0;
     return p;
 }
 
@@ -534,7 +533,7 @@ __global__ __launch_bounds__(TF_THREADS, 4) void conv_thin_out_fwd(const float *
 // 3x3, stride 1, padding 1, Cout <= 3, Cin <= 64, at least 64 K output pixels: the tap-row forward
 inline bool thin_out_fwd_ok(const ConvGeom &g, int ks, int stride) {
     return ks == 3 && stride == 1 && g.pad == 1 && g.groups == 1 && g.Cout <= 3 && g.Cin >= 16 && g.Cin <= 64 && g.Cin % 16 == 0 &&
-           (int64_t)g.B * g.Ho * g.Wo >= 64 * 1024 && dev_getenv("EBFI_NO_THIN") == nullptr && dev_getenv("EBFI_NO_THIN_FWD") == nullptr;
+           (int64_t)g.B * g.Ho * g.Wo >= 64 * 1024;
 }
 
 int launch_thin_out_fwd(hipStream_t st, const float *x, const float *w, const float *bias, float *out, const ConvGeom &g, int act,

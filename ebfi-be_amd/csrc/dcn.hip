@@ -1586,8 +1586,7 @@ extern "C" int ebfi_dcn_forward(const void *input, const void *weight, const voi
     if (B == 0) return EBFI_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // the model-shaped configuration (3x3, stride 1, dilation 1, padding 1, 8 channels per deformable group): sampling window in LDS
-    if (kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && g.cpg == 8 &&
-        !dev_getenv("EBFI_DCN_NO_WINDOW")) {
+    if (kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && g.cpg == 8) {
         const int tiles_x = (g.Wo + WPX - 1) / WPX, tiles_y = (g.Ho + WPY - 1) / WPY;
         const int64_t tiles = (int64_t)B * tiles_x * tiles_y;
         if (tiles <= 2147483647LL) {
@@ -1694,8 +1693,7 @@ extern "C" int ebfi_dcn_backward(const void *input, const void *weight, const vo
     }
     if (int rc = check_launch("dcn_bwd_data_f32")) return rc;
     int nwg = weight_grid(g);
-    const bool win = kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && g.cpg == 8 &&
-                     !dev_getenv("EBFI_DCN_NO_WINDOW");
+    const bool win = kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && g.cpg == 8;
     if (win) {
         // the model-shaped configuration: sampling window in LDS (dcn_bwd_weight_win), one workgroup per CU
         const int tiles_x = (g.Wo + WPX - 1) / WPX, tiles_y = (g.Ho + WPY - 1) / WPY;

@@ -722,7 +722,7 @@ extern "C" int ebfi_fac_backward_p16(const float *input, int input_is_unpadded, 
     if (B == 0) return EBFI_OK;
     const int64_t Hi = Ho + K - 1, Wi = Wo + K - 1, HW = (int64_t)Ho * Wo;
     const Str4 ks{(int64_t)C * K * K * HW, HW, Wo, 1}, gs{C * HW, HW, Wo, 1};
-    if (input_is_unpadded && grad_kernel16 && Wo % 8 == 0 && Wo >= 16 && dev_getenv("EBFI_FAC_BWD_X4") == nullptr) {
+    if (input_is_unpadded && grad_kernel16 && Wo % 8 == 0 && Wo >= 16) {
         // the step's configuration: eight pixels per thread, 16-byte accesses of the fp16 planes (fac_bwd_rows_p16x8)
         hipStream_t st = static_cast<hipStream_t>(stream);
         const int nxp = Wo / 8;

@@ -12,9 +12,10 @@ import threading
 
 PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))      # .../ebfi-be_amd
 REPO_ROOT = os.path.dirname(PKG_ROOT)
-# Development switches (EBFI_NO_*, EBFI_WGRAD_TR, ... -- A/B measurements and tests): honoured only in a process started with
-# EBFI_DEV=1, like the library's own (csrc/common.hpp dev_getenv), so that a stray variable cannot change which kernels a
-# production run, one of its ranks or one of its graph captures takes.
+# Development variables (EBFI_LIB_PATH below, EBFI_C16_POISON in ebfi_amd.c16): honoured only in a process started with
+# EBFI_DEV=1, so that a stray variable cannot change what a production run, one of its ranks or one of its graph captures
+# computes.  No variable selects a kernel: an A/B comparison builds the other tree into a second library (csrc/build.sh with
+# EBFI_LIB_OUT / EBFI_OBJ_DIR) and loads it here, or runs two trees.
 _DEV = os.environ.get("EBFI_DEV") == "1"
 
 
@@ -22,9 +23,9 @@ def dev_env(name, default=None):
     return os.environ.get(name, default) if _DEV else default
 
 
-# EBFI_LIB_PATH (a second build of the library for same-box A/B runs, tools/ab_bench.sh) is a development switch like the
-# others: ignored unless EBFI_DEV=1.  The ABI version of whatever is loaded must match in every case -- an older build whose
-# entry points changed signature would be called with shifted arguments (round-3 advisory).
+# EBFI_LIB_PATH: a second build of the library for same-box A/B runs (tools/ab_bench.sh).  The ABI version of whatever is
+# loaded must match in every case -- an older build whose entry points changed signature would be called with shifted
+# arguments (round-3 advisory).
 LIB_PATH = dev_env("EBFI_LIB_PATH") or os.path.join(PKG_ROOT, "lib", "libebfi_hip.so")
 HEADER = os.path.join(REPO_ROOT, "include", "ebfi_hip.h")
 BUILD_SCRIPT = os.path.join(PKG_ROOT, "csrc", "build.sh")

@@ -47,8 +47,7 @@ def _bf16_ok(k, stride, mode=None):
 def _x3_ok(k, stride, rows=None, mode=None):
     """rows: output rows of the product (Cout forward, Cin for the data gradient): 7x7 runs in split precision up to 16.
     mode: the compute mode to decide for (None = the current process-wide one)."""
-    return (mode or _COMPUTE) == "bf16x3" and stride == 1 and (k in (1, 3) or (k == 7 and rows is not None and rows <= 16 and
-                                                                               N.dev_env("EBFI_NO_CONV7X3") is None))
+    return (mode or _COMPUTE) == "bf16x3" and stride == 1 and (k in (1, 3) or (k == 7 and rows is not None and rows <= 16))
 
 
 def _bf16_ws(lib, geo, device):
@@ -288,7 +287,7 @@ def _site_backward(site, geo, act, slope, x, y, gout, need_x, need_p, unshuffle=
     # (the pixel-major kernel -- the only one for ragged Cin -- stages 16-byte quads: operands that are unaligned views
     # take the split-precision kernel instead of failing with EBFI_ERR_UNSUPPORTED)
     al16 = all(t is None or t.data_ptr() % 16 == 0 for t in (x, gout, y))
-    f16_w = f16 and (Cin % 64 == 0 or (Cin >= 32 and W % 4 == 0 and al16 and N.dev_env("EBFI_WGRAD_TR", "1") != "0"))
+    f16_w = f16 and (Cin % 64 == 0 or (Cin >= 32 and W % 4 == 0 and al16))
     f16_x = f16 and W % 4 == 0 and Cin >= 48 and site.tr16_ptr() is not None
     gpre = None
 
@@ -300,8 +299,7 @@ def _site_backward(site, geo, act, slope, x, y, gout, need_x, need_p, unshuffle=
         ws = torch.empty(max(need, 4), dtype=torch.uint8, device=x.device)
         # grad * act' for the data gradient: as the fp16 image that kernel stages (ebfi_amd.c16) when both gradients run on fp16
         # operands and the pixel-major weight-gradient kernel applies -- half the bytes written and read again
-        gpre16 = need_x and act != ACT_NONE and f16_w and f16_x and al16 and W % 4 == 0 and M % 16 == 0 and site.groups == 1 and \
-            N.dev_env("EBFI_NO_GPRE16", "0") != "1" and N.dev_env("EBFI_WGRAD_TR", "1") != "0"
+        gpre16 = need_x and act != ACT_NONE and f16_w and f16_x and al16 and W % 4 == 0 and M % 16 == 0 and site.groups == 1
         gp = None
         if need_x and act != ACT_NONE:
             if gpre16:
@@ -329,8 +327,7 @@ def _site_backward(site, geo, act, slope, x, y, gout, need_x, need_p, unshuffle=
             img = gpre is not None and gpre.dtype == torch.float16
             # (the shuffled store is the fp16 data-gradient kernel's: ungrouped, even sizes, the mask 16-byte aligned like the rest)
             native_unshuffle = unshuffle is not None and (img or (f16_x and a == ACT_NONE)) and site.groups == 1 and H % 2 == 0 and \
-                W % 4 == 0 and Cin > 32 and unshuffle[0].is_contiguous() and unshuffle[0].data_ptr() % 16 == 0 and \
-                N.dev_env("EBFI_NO_CONV_SHUFFLE", "0") != "1"
+                W % 4 == 0 and Cin > 32 and unshuffle[0].is_contiguous() and unshuffle[0].data_ptr() % 16 == 0
             if native_unshuffle:
                 gx = torch.empty((B, 4 * Cin, H // 2, W // 2), dtype=x.dtype, device=x.device)
                 in_slot = book.ptr(book.slot((site.key, "g"))) if img else book.operand((site.key, "g"), src)
@@ -411,8 +408,7 @@ def shuffle_pair_usable(x, site_a, site_b):
     """The shuffled store is the wave-specialised 3x3 kernel's: quad-aligned rows, more than 32 output channels (csrc/conv2d.hip)."""
     return (site_usable(site_a, x) and site_b is not None and site_a.ks == 3 and site_b.ks == 3 and site_a.kind == "id" and
             site_b.kind == "id" and site_a.groups == 1 and site_b.groups == 1 and site_a.M == 4 * site_b.K and site_a.M > 32 and
-            x.shape[3] % 4 == 0 and x.data_ptr() % 16 == 0 and not torch.is_autocast_enabled() and
-            N.dev_env("EBFI_NO_CONV_SHUFFLE", "0") != "1")
+            x.shape[3] % 4 == 0 and x.data_ptr() % 16 == 0 and not torch.is_autocast_enabled())
 
 
 def conv_shuffle_pair(x, site_a, slope_a, params_a, site_b, act_b, slope_b, params_b):

@@ -250,8 +250,7 @@ class FlatAdam:
         grp = self.inner.param_groups[0]
         if not (self.flat.is_cuda and self.flat.dtype == torch.float32 and flat_grad.dtype == torch.float32 and
                 flat_grad.is_contiguous() and not grp.get("amsgrad") and not grp.get("maximize") and
-                float(grp.get("weight_decay", 0.0)) == 0.0 and not torch.is_tensor(grp["lr"]) and
-                N.dev_env("EBFI_NO_NATIVE_ADAM") is None):
+                float(grp.get("weight_decay", 0.0)) == 0.0 and not torch.is_tensor(grp["lr"])):
             return False
         st = self.inner.state[self.flat]
         if not st:

@@ -82,7 +82,6 @@ class Engine:
           "all"      + every convolution of ResidualControl: 1.4-1.9e-3 -- OUTSIDE the parity bar (the twelve rounds amplify
                      the operand rounding); an experiment switch, never what bench.py or the tests run
           None       split-precision (bf16x3) forward everywhere.
-        (EBFI_DEV=1 EBFI_F16_FWD=none|filters|all overrides the argument: same-box A/B runs of bench.py.)
         backward_f16 (training, precision 'bf16x3' only; default on): the data / weight gradients of the 3x3 layers run ONE
         fp16 MFMA per product with delayed power-of-two operand scales (ebfi_amd.f16scale) instead of three bf16 ones; the
         forward pass keeps the split-precision kernels.  Gradient parity is unchanged (tests/test_gpu_model.py:
@@ -130,17 +129,16 @@ class Engine:
         # MFMA operand images of every conv weight, refreshed by one launch per step instead of one per conv call
         # (ebfi_amd.weightbank); training reads the optimiser's flat parameter buffer, inference keeps its own copy
         self.bank = None
-        from . import _native as N
         if backward_f16 is None:
-            backward_f16 = N.dev_env("EBFI_NO_F16_BWD", "0") != "1"
+            backward_f16 = True
         use_book = train and precision == "bf16x3" and backward_f16
-        forward_f16 = N.dev_env("EBFI_F16_FWD", forward_f16) if use_book else None
+        forward_f16 = forward_f16 if use_book else None
         if forward_f16 == "none":
             forward_f16 = None
         from .f16scale import FORWARD_LEVELS
         if forward_f16 not in FORWARD_LEVELS:
             raise ValueError("forward_f16 must be one of %r" % (FORWARD_LEVELS,))
-        if self.device.type == "cuda" and N.dev_env("EBFI_NO_BANK", "0") != "1":     # (switch for A/B measurements)
+        if self.device.type == "cuda":
             from . import weightbank
             self.bank = weightbank.build_for(self.model, flat=self.optimizer.flat.data, params=self.optimizer.params,
                                              fwd16=forward_f16) if train else weightbank.build_for(self.model, inference=True)

@@ -89,9 +89,8 @@ def kernelconv_fac_fused(cat, feat, site, kernel_size, slope):
                            % (site.M, site.K, B, Cin, H, W, tuple(feat.shape)))
     out = torch.empty_like(feat)
     book = site.bank.book
-    f16 = book is not None and site.fwd16_ptr() is not None and N.dev_env("EBFI_NO_FAC_F16", "0") != "1"
-    from_parts = parts is not None and len(parts) == 2 and f16 and Cin % 16 == 0 and all(int(t.shape[1]) % 8 == 0 for t in parts) and \
-        N.dev_env("EBFI_NO_FAC_IMG", "0") != "1" and N.dev_env("EBFI_NO_CAT16", "0") != "1"
+    f16 = book is not None and site.fwd16_ptr() is not None
+    from_parts = parts is not None and len(parts) == 2 and f16 and Cin % 16 == 0 and all(int(t.shape[1]) % 8 == 0 for t in parts)
     if parts is not None and not from_parts:
         cat = torch.cat(parts, 1)
     if from_parts:
@@ -122,7 +121,7 @@ def kernelconv_fac_fused(cat, feat, site, kernel_size, slope):
         scale = torch.where((amax > 0) & torch.isfinite(amax), torch.exp2(f16scale.TARGET_EXP - e), torch.ones_like(amax))
         book.slots[f16scale.SLOT_STRIDE * i:f16scale.SLOT_STRIDE * i + 1].copy_(scale.reshape(1))
         src, is_img = cat, 0
-        if Cin % 16 == 0 and N.dev_env("EBFI_NO_FAC_IMG", "0") != "1":
+        if Cin % 16 == 0:
             # the layer has C / 2 output-channel blocks and each of them stages the whole input: written once as the scaled fp16
             # image (one pass), every staging reads half the bytes and converts nothing
             from . import c16
@@ -197,7 +196,7 @@ class KernelConv2D(nn.Module):
 # bars (1e-3 / 5e-3), which tests/test_gpu_model.py::test_benchmarked_step_vs_oracle holds for the whole step.
 def kernelconv_fac_train_usable(site, book, frame, ev, ksize):
     """frame, ev: the two parts of the KernelConv's input cat([ev, frame], 1) (the concatenation itself need not exist)"""
-    if site is None or book is None or N.dev_env("EBFI_NO_C16", "0") == "1" or N.dev_env("EBFI_NO_P16", "0") == "1":
+    if site is None or book is None:
         return False
     B, Cf, H, W = frame.shape
     Cin = Cf + ev.shape[1]
@@ -229,7 +228,7 @@ class KernelConvFacTrain(Function):
         with torch.cuda.device_of(ev):
             st = N.stream_ptr(ev.device)
             cat = None
-            if f16_fwd and C % 8 == 0 and frame.shape[1] % 8 == 0 and N.dev_env("EBFI_NO_CAT16", "0") != "1":
+            if f16_fwd and C % 8 == 0 and frame.shape[1] % 8 == 0:
                 cat16 = c16.to_c16_cat2(ev, frame, sp("x"))       # the image of the concatenation from its two parts
             else:
                 cat = torch.cat([ev, frame], 1)

@@ -210,8 +210,7 @@ def conv_transpose3d_se(x, m, attn_conv, act=0, slope=0.0):
     UNet3d_18, model_singleframe.py:200-221): the gate reads the folded convolution's output through the pixel shuffle."""
     B, Ci, D, H, W = x.shape
     C = m.out_channels
-    if N.dev_env("EBFI_NO_SEGATE_SHUFFLE", "0") != "1" and N.dev_env("EBFI_NO_SEGATE", "0") != "1" and x.is_cuda \
-            and x.dtype == torch.float32 and W % 2 == 0 and B * C <= 4096 and attn_conv.in_channels == attn_conv.out_channels == C \
+    if x.is_cuda and x.dtype == torch.float32 and W % 2 == 0 and B * C <= 4096 and attn_conv.in_channels == attn_conv.out_channels == C \
             and not torch.is_autocast_enabled():
         return _SEGateShuffled.apply(_conv_transpose3d_unshuffled(x, m), attn_conv.weight, attn_conv.bias, int(act), float(slope))
     return se_gate(conv_transpose3d_d2(x, m), attn_conv, None, act, slope)
@@ -262,9 +261,7 @@ def se_gate(x, attn_conv, res=None, act=0, slope=0.0):
     (model_singleframe.py:213-221) do right after the gate."""
     B, C = x.shape[0], x.shape[1]
     n = x.numel() // max(B * C, 1)
-    import os
-    if N.dev_env("EBFI_NO_SEGATE", "0") != "1" and \
-            x.is_cuda and x.dtype == torch.float32 and n % 4 == 0 and B * C <= 4096 and attn_conv.in_channels == attn_conv.out_channels == C \
+    if x.is_cuda and x.dtype == torch.float32 and n % 4 == 0 and B * C <= 4096 and attn_conv.in_channels == attn_conv.out_channels == C \
             and (res is None or res.shape == x.shape) and not torch.is_autocast_enabled():
         return _SEGate.apply(x, attn_conv.weight, attn_conv.bias, res, int(act), float(slope))
     pooled = x.mean(dim=(2, 3, 4))

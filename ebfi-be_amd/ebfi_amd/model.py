@@ -21,7 +21,6 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _native as N
 from . import conv, fold3d, fused, norm
 from .blur import Frame2DCP, Frame2Lap
 from .fac import KernelConv2D
@@ -225,8 +224,7 @@ class Modification(BaseModel):
         if torch.is_grad_enabled() and (ev.requires_grad or frame.requires_grad or any(p.requires_grad for p in self.KernelConv.parameters())):
             return None
         if conv.get_compute_dtype() != "bf16x3" or not frame.is_cuda or frame.dtype != torch.float32 or ev.dtype != torch.float32 or \
-                frame.shape[-1] % 4 != 0 or frame.shape[0] != ev.shape[0] or frame.shape[2:] != ev.shape[2:] or \
-                N.dev_env("EBFI_NO_FAC_FUSION", "0") == "1":
+                frame.shape[-1] % 4 != 0 or frame.shape[0] != ev.shape[0] or frame.shape[2:] != ev.shape[2:]:
             return None
         site = weightbank.lookup(self.KernelConv.conv2d.weight, "facrows")
         if site is None:
@@ -254,7 +252,7 @@ class Modification(BaseModel):
             return FrameTensor * ev1 + self.Conv2(ev1)
         cat = torch.cat([ev, FrameTensor], dim=1)
         fuse = self.KernelConv.native(cat)
-        if fuse is not None and fuse[0] == conv.ACT_LEAKY and ev.is_cuda and N.dev_env("EBFI_NO_PREACT", "0") != "1":
+        if fuse is not None and fuse[0] == conv.ACT_LEAKY and ev.is_cuda:
             # the 1600-channel filter tensor has one consumer, the FAC op: its backward returns the gradient of the filters'
             # PRE-activation (kernel > 0 ? g : slope*g), so the 128 -> 1600 conv's weight / data gradient neither re-read the
             # 839 MB saved output for act' nor write / read a grad*act' side tensor of that size
@@ -442,7 +440,7 @@ class UNet3d_18(nn.Module):
         y = self.decoder[4](y, slope)
         ff, oc = self.feature_fuse[0], self.outconv[1]
         from . import weightbank
-        site = weightbank.lookup(ff.weight, "fuse_d2") if N.dev_env("EBFI_NO_FUSE_D2", "0") != "1" else None
+        site = weightbank.lookup(ff.weight, "fuse_d2")
         if site is not None and y.is_contiguous() and conv.site_usable(site, y.reshape(y.shape[0], -1, y.shape[3], y.shape[4])) and \
                 not torch.is_autocast_enabled():
             # cat(unbind(y, 2), 1) is a channel permutation of y's own memory: the 1x1 fuse reads y in place through the bank's

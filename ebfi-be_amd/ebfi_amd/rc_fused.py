@@ -138,16 +138,12 @@ def _slot_keys(sites):
 def _tail_in_epilogue(book, sites):
     """Round 5: the round's tail (scale, residual, concat) runs in the epilogue of its grouped convolution (csrc/conv2d.hip
     EpiExtra post_scale / pre16) once the slot of the activation image `a` has been calibrated by the layer-wise form."""
-    if N.dev_env("EBFI_NO_RC_EPILOGUE", "0") == "1":          # (development switch: same-box A/B against the separate stage)
-        return False
     return all(book.index.get((sb.key, "a")) in book.calibrated for _, sb, _ in sites)
 
 
 def images_usable(book, sites, W):
     """The image path needs every operand slot of the module calibrated (the layer-wise form below measures them just in time
     on the first eager pass and during the engine's calibration steps) and rows that split into 16-byte quads."""
-    if N.dev_env("EBFI_NO_C16", "0") == "1":          # (development switch: same-box A/B of the two forms)
-        return False
     if book is None or W % 4 != 0 or any(sa.tr16_ptr() is None or sb.tr16_ptr() is None or sc.tr16_ptr() is None for sa, sb, sc in sites):
         return False
     return all(book.index.get(k) in book.calibrated for k in _slot_keys(sites))
@@ -283,11 +279,10 @@ class ResidualControlFn(Function):
                         _conv16(lib, st, x, sa, sa.bias(), ya, B, C, H, W, 2 * C, 1, slope, ya16, sp(sb, "x"))
                         _conv(lib, st, ya, sb.fwd_ptr(), sb.fwd_bytes, sb.bias(), a, B, C, H, W, 2 * C, 2, ACT, slope)
                         # the epilogue-tail form above needs the slot of the image of `a`, which only the layer-wise form used to
-                        # measure: slots restored from an earlier state, or a first pass run with EBFI_NO_RC_EPILOGUE=1, left this
-                        # path on the separate stage for good (round-5 advisory).  Measured here while the fp32 `a` still exists
+                        # measure: slots restored from an earlier state left this path on the separate stage for good (round-5
+                        # advisory).  Measured here while the fp32 `a` still exists
                         # (eager passes only: a first use cannot be calibrated inside a graph capture).
-                        if book.index.get((sb.key, "a")) not in book.calibrated and not torch.cuda.is_current_stream_capturing() \
-                                and N.dev_env("EBFI_NO_RC_EPILOGUE", "0") != "1":
+                        if book.index.get((sb.key, "a")) not in book.calibrated and not torch.cuda.is_current_stream_capturing():
                             book.operand((sb.key, "a"), a)
                     rc = lib.ebfi_scale_residual_cat_forward_c16(N.ptr(a), N.ptr(s_ex[i]), N._vp(a.data_ptr() + 4 * C * HW), N.ptr(s_t[i]),
                                                                  N.ptr(x), N.ptr(c), N.ptr(c16i), sp(sc, "x"), B, C, H, W, 2 * C * HW, st)
@@ -309,7 +304,7 @@ class ResidualControlFn(Function):
             new = lambda ch: torch.empty((B, ch, H, W), dtype=x.dtype, device=x.device)
             # inference: the round's tail in the grouped convolution's epilogue (scale + residual only, no images): one launch and
             # one [B, 2C, H, W] tensor less per round -- 0.39 ms and 3.8 GB of traffic each at B=8 720x1280
-            tail = not keep and W % 4 == 0 and C % 64 == 0 and x.data_ptr() % 16 == 0 and N.dev_env("EBFI_NO_RC_EPILOGUE", "0") != "1"
+            tail = not keep and W % 4 == 0 and C % 64 == 0 and x.data_ptr() % 16 == 0
             s_cat = torch.cat([s_ex, s_t], 2).contiguous() if tail else None
             for i, (sa, sb, sc) in enumerate(sites):
                 if tail:
@@ -366,7 +361,7 @@ class ResidualControlFn(Function):
                 # image of the last round's pre-activation gradient (later rounds get theirs from the data gradient's epilogue)
                 g5 = c16.to_c16(gout.contiguous(), sp(sites[-1][2], "g"), xlast, slope)
                 # (every layer of a round is two 64 x 64 blocks exactly when C == 64; enough 4 x 32 pixel tiles for the 40 splits)
-                batch = C == 64 and B * ((H + 3) // 4) * ((W + 31) // 32) >= 40 and N.dev_env("EBFI_NO_WGRAD_BATCH", "0") != "1"
+                batch = C == 64 and B * ((H + 3) // 4) * ((W + 31) // 32) >= 40
                 gdata = None
                 for i in range(nstep - 1, -1, -1):
                     sa, sb, sc = sites[i]

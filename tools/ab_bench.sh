@@ -1,6 +1,7 @@
 #!/bin/bash
-# Same-box A/B of bench.py configurations (development): each line of output = one configuration's headline numbers.
-# usage (GPU box; files under $AB_OUT, default output/ab): tools/ab_bench.sh "NAME=ENV1=v ENV2=v" ...   e.g.  tools/ab_bench.sh "prev=EBFI_LIB_PATH=$PWD/ebfi-be_amd/lib/libebfi_hip_prev.so EBFI_NO_BANK=1" "new="
+# Same-box A/B of library builds (development): each line of output = one arm's headline numbers.  The other tree is built
+# into a second library first (EBFI_LIB_OUT=... EBFI_OBJ_DIR=... bash ebfi-be_amd/csrc/build.sh).
+# usage (GPU box; files under $AB_OUT, default output/ab): tools/ab_bench.sh "NAME=ENV1=v ENV2=v" ...   e.g.  tools/ab_bench.sh "prev=EBFI_LIB_PATH=$PWD/ebfi-be_amd/lib/libebfi_hip_prev.so" "new="
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT="${AB_OUT:-output/ab}"
 mkdir -p "$OUT"

@@ -151,16 +151,12 @@ int main(int argc, char **argv) {
         if (ebfi_conv2d_forward(x, w, bias, y_ref, B, Cin, H, W, Cout, 3, 1, 1, 1, 0.01f, EBFI_F32, nullptr)) { fprintf(stderr, "%s\n", ebfi_last_error()); return 3; }
         std::vector<Variant> vs;
         vs.push_back({"fwd fp32 exact (library)", [&] { return ebfi_conv2d_forward(x, w, bias, y, B, Cin, H, W, Cout, 3, 1, 1, 1, 0.01f, EBFI_F32, nullptr); }, {}});
-        auto with_vec = [&](const char *v, std::function<int()> f) { return [=] { setenv("EBFI_CONV_VEC", v, 1); int rc = f(); unsetenv("EBFI_CONV_VEC"); return rc; }; };
         auto fwd = [&] { return ebfi_conv2d_forward_bf16x3(x, w, bias, y, B, Cin, H, W, Cout, 3, 1, 1, 1, 0.01f, ws, wsb, nullptr); };
         auto dg_act = [&] { return ebfi_conv2d_backward_data_bf16x3(g, y_ref, w, gx, B, Cin, H, W, Cout, 3, 1, 1, 1, 0.01f, ws, wsb, nullptr); };
         auto dg = [&] { return ebfi_conv2d_backward_data_bf16x3(g, nullptr, w, gx, B, Cin, H, W, Cout, 3, 1, 1, 0, 0.f, ws, wsb, nullptr); };
-        vs.push_back({"fwd x3 one tile per workgroup", [&] { setenv("EBFI_CONV_NOPERSIST", "1", 1); int rc = fwd(); unsetenv("EBFI_CONV_NOPERSIST"); return rc; }, {}});
-        vs.push_back({"fwd x3 persistent over tiles", with_vec("1", fwd), {}});
-        vs.push_back({"fwd x3 quad ld / dword st", with_vec("4", fwd), {}});
-        vs.push_back({"dgrad x3 act' folded, dword", with_vec("1", dg_act), {}});
-        vs.push_back({"dgrad x3 act' folded, quad", with_vec("4", dg_act), {}});
-        vs.push_back({"dgrad x3 plain, quad", with_vec("4", dg), {}});
+        vs.push_back({"fwd x3 (library)", fwd, {}});
+        vs.push_back({"dgrad x3 act' folded (library)", dg_act, {}});
+        vs.push_back({"dgrad x3 plain (library)", dg, {}});
         time_variants(vs, 7, 20);
         ebfi_conv2d_forward_bf16x3(x, w, bias, y, B, Cin, H, W, Cout, 3, 1, 1, 1, 0.01f, ws, wsb, nullptr);
         CK(hipDeviceSynchronize());
@@ -181,8 +177,7 @@ int main(int argc, char **argv) {
         if (ebfi_conv2d_backward_weight(x, g, y_ref, gw_ref, gb, B, Cin, H, W, Cout, 3, 1, 1, 0, 0.f, wgs, wgb, EBFI_F32, nullptr)) { fprintf(stderr, "%s\n", ebfi_last_error()); return 3; }
         std::vector<Variant> vs;
         vs.push_back({"wgrad fp32 exact (library)", [&] { return ebfi_conv2d_backward_weight(x, g, y_ref, gw, gb, B, Cin, H, W, Cout, 3, 1, 1, 0, 0.f, wgs, wgb, EBFI_F32, nullptr); }, {}});
-        vs.push_back({"wgrad x3 512 thr x 64 ch, 1 WG/CU", [&] { setenv("EBFI_WGRAD_BIGWG", "1", 1); int rc = ebfi_conv2d_backward_weight(x, g, y_ref, gw, gb, B, Cin, H, W, Cout, 3, 1, 1, 0, 0.f, wgs, wgb, EBFI_F32_BF16X3MMA, nullptr); unsetenv("EBFI_WGRAD_BIGWG"); return rc; }, {}});
-        vs.push_back({"wgrad x3 256 thr x 32 ch, 2 WG/CU", [&] { return ebfi_conv2d_backward_weight(x, g, y_ref, gw, gb, B, Cin, H, W, Cout, 3, 1, 1, 0, 0.f, wgs, wgb, EBFI_F32_BF16X3MMA, nullptr); }, {}});
+        vs.push_back({"wgrad x3 (library)", [&] { return ebfi_conv2d_backward_weight(x, g, y_ref, gw, gb, B, Cin, H, W, Cout, 3, 1, 1, 0, 0.f, wgs, wgb, EBFI_F32_BF16X3MMA, nullptr); }, {}});
         vs.push_back({"wgrad bf16x3 act' folded + side out", [&] { return ebfi_conv2d_backward_weight_ex(x, g, y_ref, gw, gb, y, B, Cin, H, W, Cout, 3, 1, 1, 1, 0.01f, wgs, wgb, EBFI_F32_BF16X3MMA, nullptr); }, {}});
         time_variants(vs, 7, 20);
         ebfi_conv2d_backward_weight(x, g, y_ref, gw, gb, B, Cin, H, W, Cout, 3, 1, 1, 0, 0.f, wgs, wgb, EBFI_F32_BF16X3MMA, nullptr);
