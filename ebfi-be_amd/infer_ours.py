@@ -19,8 +19,15 @@ writes, per clip, `<output_path>/<clip name>/restored.npz` (`restored` float32 [
 `exposure_duty`, `timestamps`) and -- with --png, when PIL is importable -- the reference's image tree
 `<clip name>/img/{restored_frame/%09d_%d.png, blurry_frame/%09d.png, gt_frame/%09d_%d.png}`.
 
-Not done here (out of the hot path's scope): PSNR / SSIM / LPIPS (skimage, lpips are not part of the image), the
-event visualisations, the yaml loggers, `--real_blur` clips (a different dataset class).  A knob this reader cannot honour
+Every restored timestamp is scored against the clip's sharp frame (infer_ours.py:120-128; --no-metrics switches it off): PSNR,
+SSIM and MSE as loss/restore.py:43-92 and nn.MSELoss define them, computed on the device by ebfi_amd.metrics -- one call per
+load, after the timed model interval -- and written as the reference writes them (:136-152, :340-417):
+`<clip name>/inference.yml` (`evaluation results`: the clip's averages; `evaluation step results`: the per-timestamp psnr list)
+and, after the last clip, `inference_all.yml` (per-clip breakdown, mean over clips) and `inference_all_step.yml` (per-step mean
+over the shortest list); `restored.npz` also carries `psnr` / `ssim` / `mse` [loads, NumF].
+
+Not done here (out of the hot path's scope): LPIPS (its AlexNet trunk weights are a torchvision download; the key is
+left out and reported), the event visualisations, `--real_blur` clips (a different dataset class).  A knob this reader cannot honour
 is reported on stderr, never dropped silently.  Without --data_list the script runs a synthetic clip (BASELINE.json configs
 1 / 2 / 5):
 
@@ -30,6 +37,7 @@ is reported on stderr, never dropped silently.  Without --data_list the script r
     run writes checkpoint-iteration99.pth and is resumed at iteration 100)
 """
 import argparse
+import json
 import os
 import sys
 import time
@@ -93,6 +101,8 @@ def get_flags(argv=None):
     ap.add_argument("--real_blur", default=False, action="store_true")
     # ---- this implementation's own ----
     ap.add_argument("--png", action="store_true", help="also write the reference's PNG tree (needs PIL)")
+    ap.add_argument("--no-metrics", action="store_true",
+                    help="with --data_list: do not score the restored frames against the clip's sharp frames (PSNR / SSIM / MSE)")
     ap.add_argument("--data_seed", type=int, default=123, help="base of the per-item seeds (noise draw); the reference seeds "
                                                                 "python's generator with 123 and draws one seed per item")
     ap.add_argument("--batch", type=int, default=4, help="synthetic mode (no --data_list)")
@@ -165,11 +175,54 @@ def write_png(path, chw):
     Image.fromarray(arr).save(path)
 
 
+def mean_per_step(lists):
+    """infer_ours.py:175-190 (process): the mean over the clips of each step's value, over the length of the shortest list."""
+    n = min((len(v) for v in lists), default=0)
+    return [float(np.mean([v[i] for v in lists])) for i in range(n)]
+
+
+def write_results(path, content):
+    """The reference's Logger_yaml (myutils/utils.py:218-230): one yaml.dump of the dict.  Without PyYAML the same dict goes to
+    `<path minus .yml>.json` (reported on stderr).  Returns the path written."""
+    try:
+        import yaml
+    except ImportError:
+        yaml = None
+    if yaml is None:
+        path = os.path.splitext(path)[0] + ".json"
+        warn("PyYAML is not importable: writing %s as JSON" % path)
+        with open(path, "w") as f:
+            json.dump(content, f, indent=1, sort_keys=True)
+        return path
+    with open(path, "w") as f:
+        yaml.dump(content, f)
+    return path
+
+
+def summarise_clips(results, info):
+    """infer_ours.py:386-417: the contents of inference_all.yml and inference_all_step.yml from the per-clip results
+    [(clip name, {metric: clip average}, {"psnr": per-step list})]."""
+    breakdown, means, breakdown_step, means_step = {}, {}, {}, {}
+    for name, result, result_step in results:
+        for k, v in result.items():
+            breakdown.setdefault(k, {})[name] = float(v)
+            means.setdefault(k, []).append(float(v))
+        for k, v in result_step.items():
+            breakdown_step.setdefault(k, {})[name] = [float(x) for x in v]
+            means_step.setdefault(k, []).append(list(v))
+    all_ = {"info": [info], "breakdown results for each data": breakdown,
+            "mean results for the whole data": {k: float(np.mean(v)) for k, v in means.items()}}
+    all_step = {"info": [info], "breakdown results for each data": breakdown_step,
+                "mean results for the whole data (based on min length)": {k: mean_per_step(v) for k, v in means_step.items()}}
+    return all_, all_step
+
+
 @torch.no_grad()
-def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False):
+def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, metrics=True, info=""):
     """infer_body of the reference for one clip: every sequence, every load, every latent timestamp; returns
-    (frames written, seconds inside the model)."""
+    (frames written, seconds inside the model, (result, result_step) or None without metrics)."""
     from ebfi_amd import clipdata
+    from ebfi_amd.metrics import MetricTracker, frame_metrics
     name = os.path.basename(data_path)
     data = clipdata.ClipDataset(data_path, time_bins=int(ds_cfg["time_bins"]), frames_per_period=int(ds_cfg["NumFramePerPeriod"]),
                                 frames_per_blurry=int(ds_cfg["NumFramePerBlurry"]), exposure_method=ds_cfg["ExposureMethod"],
@@ -184,6 +237,9 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False):
         for sub in ("blurry_frame", "gt_frame", "restored_frame"):
             os.makedirs(os.path.join(img_path, sub), exist_ok=False)
     restored, blurry, duties, stamps, loads = [], [], [], [], []
+    scores = []                                            # per load: [3 (psnr, ssim, mse), NumF]
+    track = MetricTracker(["mse", "psnr", "ssim"])
+    step = {"psnr": []}
     iL = iF = -1
     spent = 0.0
     for si, seq in enumerate(seqs):
@@ -199,7 +255,17 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False):
             pred = interp(frame.contiguous(), event.contiguous(), duty.contiguous(), [float(v) for v in ts.tolist()])
             torch.cuda.synchronize(device)
             spent += time.perf_counter() - t0
+            if metrics:                                    # (after the timed interval: the frames/s line keeps its meaning)
+                psnr, ssim, mse = frame_metrics(pred[0], item["SeqLatentF"][0, 0])
             restored.append(pred[0].cpu().numpy())          # [NumF, 3, H, W]
+            if metrics:
+                sc = torch.stack((psnr, ssim, mse)).cpu().numpy()
+                scores.append(sc)
+                for p_, s_, m_ in sc.T:                    # (per timestamp, in the reference's order)
+                    step["psnr"].append(float(p_))
+                    track.update("mse", float(m_))
+                    track.update("psnr", float(p_))
+                    track.update("ssim", float(s_))
             blurry.append(frame[0].cpu().numpy())
             duties.append(float(duty.item()))
             stamps.append(ts.cpu().numpy())
@@ -212,10 +278,21 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False):
             if png:
                 write_png(os.path.join(img_path, "blurry_frame", "%09d.png" % iL), frame[0])
     if restored:
+        extra = {}
+        if metrics:
+            sc = np.stack(scores)
+            extra = dict(psnr=sc[:, 0], ssim=sc[:, 1], mse=sc[:, 2])
         np.savez(os.path.join(root_path, "restored.npz"), restored=np.stack(restored), blurry=np.stack(blurry),
-                 exposure_duty=np.array(duties, dtype=np.float32), timestamps=np.stack(stamps), period=np.array(loads))
+                 exposure_duty=np.array(duties, dtype=np.float32), timestamps=np.stack(stamps), period=np.array(loads), **extra)
     print("%s: %d loads, %d frames restored -> %s" % (name, iL + 1, iF + 1, root_path), flush=True)
-    return iF + 1, spent
+    if not metrics:
+        return iF + 1, spent, None
+    result = track.result()
+    write_results(os.path.join(root_path, "inference.yml"), {"info": [info], "evaluation results": result,
+                                                              "evaluation step results": step})
+    print("%s: psnr %.4f  ssim %.4f  mse %.6g over %d frames" % (name, result["psnr"], result["ssim"], result["mse"], iF + 1),
+          flush=True)
+    return iF + 1, spent, (result, step)
 
 
 def run_data_list(flags, interp, device):
@@ -235,13 +312,25 @@ def run_data_list(flags, interp, device):
         except ImportError:
             warn("--png needs PIL, which is not importable: writing restored.npz only")
             png = False
-    frames, spent = 0, 0.0
+    metrics = not flags.no_metrics
+    if metrics:
+        from ebfi_amd.metrics import LPIPS_UNAVAILABLE
+        warn(LPIPS_UNAVAILABLE + "; psnr / ssim / mse only")
+    frames, spent, results = 0, 0.0, []
     for k, data_path in enumerate(paths):
         print("processing %s" % data_path, flush=True)
-        n, s = infer_clip(interp, data_path, ds_cfg, os.path.join(flags.output_path, os.path.basename(data_path)), device,
-                          seed=flags.data_seed + 100003 * k, png=png)
+        n, s, r = infer_clip(interp, data_path, ds_cfg, os.path.join(flags.output_path, os.path.basename(data_path)), device,
+                             seed=flags.data_seed + 100003 * k, png=png, metrics=metrics,
+                             info="inference %s on %s" % ([flags.model_path], data_path))
         frames, spent = frames + n, spent + s
+        if r is not None:
+            results.append((os.path.basename(data_path),) + r)
     print("restored %d frames of %d clip(s) in %.3f s inside the model: %.1f frames/s" % (frames, len(paths), spent, frames / max(spent, 1e-9)))
+    if metrics:
+        # (written once every clip is done: a run refused half-way leaves an earlier run's summaries as they were)
+        all_, all_step = summarise_clips(results, "inference %s \n on %s" % ([flags.model_path], paths))
+        write_results(os.path.join(flags.output_path, "inference_all.yml"), all_)
+        write_results(os.path.join(flags.output_path, "inference_all_step.yml"), all_step)
 
 
 @torch.no_grad()

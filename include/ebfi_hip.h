@@ -36,6 +36,7 @@
  *   ebfi_gather_sum             weight re-layouts of the depth-2 Conv3d / ConvTranspose3d (models/model_misc/resnet_3D.py)
  *   ebfi_events_to_stack        dataloader/encodings.py:307-350 (events_to_stack)
  *   ebfi_frame2lap / _frame2dcp myutils/utils.py:34-49 / :15-31
+ *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
  */
 #ifndef EBFI_HIP_H
 #define EBFI_HIP_H
@@ -69,7 +70,10 @@ extern "C" {
  *  12  ebfi_se_gate_forward_ps / _backward_ps (the squeeze-excite gate of an up-convolution stage reading the transposed
  *      convolution's output through the pixel shuffle)
  *  13  ebfi_conv2d_packed_x3_shuffled / ebfi_conv2d_packed_f16_shuffled (convolutions storing through PixelShuffle(2) / its inverse)
- *  14  ebfi_to_c16_cat2 (the fp16 image of a two-part channel concatenation without the concatenated tensor) */
+ *  14  ebfi_to_c16_cat2 (the fp16 image of a two-part channel concatenation without the concatenated tensor); later, as a pure
+ *      addition under the same number, ebfi_image_metrics_workspace / ebfi_image_metrics (evaluation PSNR / SSIM / MSE): no
+ *      existing entry point changed, so a caller built against an earlier 14 header still calls every function it knows with
+ *      the right arguments, and the binding's version check has nothing new to refuse */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -603,6 +607,29 @@ int ebfi_adam_step_guarded(float *param, const float *grad, float *exp_avg, floa
 int ebfi_grad_gather(const void *const *grads, const int64_t *numels, int count, float *flat, int64_t total, int pad,
                      const int *guard, void *stream);
 
+
+/* ------------------------------------------------------------------ evaluation metrics
+ * Per frame n of an fp32 pair pred / target [N, C, H, W] (the evaluation loop's psnr_loss / ssim_loss / nn.MSELoss,
+ * loss/restore.py:43-92, one reference call per frame):
+ *   ssim[n] = mean over c of the mean over the interior pixels [3, H-3) x [3, W-3) of the SSIM map of scikit-image's
+ *             structural_similarity defaults: 7x7 uniform window, sample covariance (x 49/48), C1 = (0.01 R)^2, C2 = (0.03 R)^2,
+ *             R = ssim_data_range (2 reproduces the reference's float32 call without data_range)
+ *   psnr[n] = C >= 2: mean over c of 10 log10(dr_c^2 / mse_c), mse_c = mean((target_c - pred_c)^2) unclipped,
+ *             dr_c = max(target_c) - min(target over all channels) (the reference's data range);
+ *             C == 1: 10 log10(1 / mse) of both images clipped to [0, 1]
+ *   mse[n]  = mean((pred - target)^2) over C*H*W
+ * A non-finite value anywhere in frame n's pred or target makes its three outputs NaN; mse_c = 0 gives +inf.
+ * Strides (elements, any int64) of N, C and rows; the column stride must be 1 (EBFI_ERR_UNSUPPORTED otherwise).  16-byte row
+ * loads when both base pointers are 16-byte aligned and all strides are multiples of 4, scalar loads otherwise.
+ * Two launches on `stream` (per-tile partials into `workspace`, then a fixed-order fp64 reduction per frame): no host
+ * synchronisation, no allocation, no atomics -- capturable, and bit-reproducible.  workspace: 16-byte aligned, at least
+ * ebfi_image_metrics_workspace(N, C, H, W) bytes (pure host arithmetic; 0 for a bad shape).  out_*: device float[N].
+ * Null pointers, C < 1, H < 7 or W < 7 (scikit-image refuses a window larger than the image) or a ssim_data_range that is
+ * not positive -> EBFI_ERR_ARG; a short workspace -> EBFI_ERR_WORKSPACE; neither touches the GPU. */
+int64_t ebfi_image_metrics_workspace(int64_t N, int C, int H, int W);
+int ebfi_image_metrics(const float *pred, const int64_t pred_strides[4], const float *target, const int64_t target_strides[4],
+                       int64_t N, int C, int H, int W, float ssim_data_range, void *workspace, int64_t workspace_bytes,
+                       float *out_psnr, float *out_ssim, float *out_mse, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
