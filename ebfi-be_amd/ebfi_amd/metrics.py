@@ -6,7 +6,9 @@ the current stream, no host synchronisation -- and returns device tensors ``(psn
 (include/ebfi_hip.h): PSNR with the reference's per-channel data range (one-channel images clipped to [0, 1], range 1), SSIM
 of scikit-image's structural_similarity defaults (7x7 uniform window, sample covariance, interior mean) with data range
 ``ssim_data_range`` (2.0: what the reference's float32 call without data_range uses), MSE over C*H*W.  A NaN or inf in a
-frame makes its three values NaN.  LPIPS is not computed: its AlexNet trunk weights are a torchvision download.
+frame makes its three values NaN.  LPIPS is ebfi_amd.lpips: it needs two weight files named by the caller (the reference's
+v0.1 heads and torchvision's AlexNet trunk), which no download supplies here; without them it is left out and LPIPS_UNAVAILABLE
+says why.
 """
 import torch
 

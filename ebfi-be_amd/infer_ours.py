@@ -24,12 +24,15 @@ SSIM and MSE as loss/restore.py:43-92 and nn.MSELoss define them, computed on th
 load, after the timed model interval -- and written as the reference writes them (:136-152, :340-417):
 `<clip name>/inference.yml` (`evaluation results`: the clip's averages; `evaluation step results`: the per-timestamp psnr list)
 and, after the last clip, `inference_all.yml` (per-clip breakdown, mean over clips) and `inference_all_step.yml` (per-step mean
-over the shortest list); `restored.npz` also carries `psnr` / `ssim` / `mse` [loads, NumF].
+over the shortest list); `restored.npz` also carries `psnr` / `ssim` / `mse` [loads, NumF].  LPIPS (AlexNet, v0.1, the
+reference's fourth metric) is scored too when both of its weight files are named -- `--lpips_lin` the reference's
+loss/PerceptualSimilarity/models/weights/v0.1/alex.pth, `--lpips_backbone` torchvision's AlexNet state dict
+(alexnet-owt-7be5be79.pth) -- by ebfi_amd.lpips on the device, after the timed interval like the others: `lpips` then appears
+in the three yml files and in restored.npz.  Without them the key is left out and stderr says so.
 
-Not done here (out of the hot path's scope): LPIPS (its AlexNet trunk weights are a torchvision download; the key is
-left out and reported), the event visualisations, `--real_blur` clips (a different dataset class).  A knob this reader cannot honour
-is reported on stderr, never dropped silently.  Without --data_list the script runs a synthetic clip (BASELINE.json configs
-1 / 2 / 5):
+Not done here (out of the hot path's scope): the event visualisations, `--real_blur` clips (a different dataset
+class).  A knob this reader cannot honour is reported on stderr, never dropped silently.  Without --data_list the script runs a
+synthetic clip (BASELINE.json configs 1 / 2 / 5):
 
     python infer_ours.py --model_path output/models/Ours/run/checkpoint-iteration99.pth --batch 4 --height 256 --width 256
     python infer_ours.py --batch 1 --height 128 --width 128 --rand-init
@@ -103,6 +106,11 @@ def get_flags(argv=None):
     ap.add_argument("--png", action="store_true", help="also write the reference's PNG tree (needs PIL)")
     ap.add_argument("--no-metrics", action="store_true",
                     help="with --data_list: do not score the restored frames against the clip's sharp frames (PSNR / SSIM / MSE)")
+    ap.add_argument("--lpips_lin", type=str, default=None,
+                    help="LPIPS: the reference's linear heads, loss/PerceptualSimilarity/models/weights/v0.1/alex.pth (with "
+                         "--lpips_backbone, the metrics also score LPIPS)")
+    ap.add_argument("--lpips_backbone", type=str, default=None,
+                    help="LPIPS: torchvision's AlexNet state dict (alexnet-owt-7be5be79.pth of the torch hub cache)")
     ap.add_argument("--data_seed", type=int, default=123, help="base of the per-item seeds (noise draw); the reference seeds "
                                                                 "python's generator with 123 and draws one seed per item")
     ap.add_argument("--batch", type=int, default=4, help="synthetic mode (no --data_list)")
@@ -218,9 +226,10 @@ def summarise_clips(results, info):
 
 
 @torch.no_grad()
-def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, metrics=True, info=""):
+def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, metrics=True, info="", lpips=None):
     """infer_body of the reference for one clip: every sequence, every load, every latent timestamp; returns
-    (frames written, seconds inside the model, (result, result_step) or None without metrics)."""
+    (frames written, seconds inside the model, (result, result_step) or None without metrics).  lpips: an
+    ebfi_amd.lpips.AlexLPIPS that scores LPIPS as a fourth metric, or None."""
     from ebfi_amd import clipdata
     from ebfi_amd.metrics import MetricTracker, frame_metrics
     name = os.path.basename(data_path)
@@ -237,8 +246,8 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, me
         for sub in ("blurry_frame", "gt_frame", "restored_frame"):
             os.makedirs(os.path.join(img_path, sub), exist_ok=False)
     restored, blurry, duties, stamps, loads = [], [], [], [], []
-    scores = []                                            # per load: [3 (psnr, ssim, mse), NumF]
-    track = MetricTracker(["mse", "psnr", "ssim"])
+    scores = []                                            # per load: [3 (psnr, ssim, mse) or 4 (+ lpips), NumF]
+    track = MetricTracker(["mse", "psnr", "ssim"] + (["lpips"] if lpips is not None else []))
     step = {"psnr": []}
     iL = iF = -1
     spent = 0.0
@@ -257,15 +266,20 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, me
             spent += time.perf_counter() - t0
             if metrics:                                    # (after the timed interval: the frames/s line keeps its meaning)
                 psnr, ssim, mse = frame_metrics(pred[0], item["SeqLatentF"][0, 0])
+                per_load = [psnr, ssim, mse]
+                if lpips is not None:
+                    per_load.append(lpips(pred[0], item["SeqLatentF"][0, 0], normalize=True))
             restored.append(pred[0].cpu().numpy())          # [NumF, 3, H, W]
             if metrics:
-                sc = torch.stack((psnr, ssim, mse)).cpu().numpy()
+                sc = torch.stack(per_load).cpu().numpy()
                 scores.append(sc)
-                for p_, s_, m_ in sc.T:                    # (per timestamp, in the reference's order)
-                    step["psnr"].append(float(p_))
-                    track.update("mse", float(m_))
-                    track.update("psnr", float(p_))
-                    track.update("ssim", float(s_))
+                for v in sc.T:                             # (per timestamp, in the reference's order)
+                    step["psnr"].append(float(v[0]))
+                    track.update("mse", float(v[2]))
+                    track.update("psnr", float(v[0]))
+                    track.update("ssim", float(v[1]))
+                    if lpips is not None:
+                        track.update("lpips", float(v[3]))
             blurry.append(frame[0].cpu().numpy())
             duties.append(float(duty.item()))
             stamps.append(ts.cpu().numpy())
@@ -282,6 +296,8 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, me
         if metrics:
             sc = np.stack(scores)
             extra = dict(psnr=sc[:, 0], ssim=sc[:, 1], mse=sc[:, 2])
+            if lpips is not None:
+                extra["lpips"] = sc[:, 3]
         np.savez(os.path.join(root_path, "restored.npz"), restored=np.stack(restored), blurry=np.stack(blurry),
                  exposure_duty=np.array(duties, dtype=np.float32), timestamps=np.stack(stamps), period=np.array(loads), **extra)
     print("%s: %d loads, %d frames restored -> %s" % (name, iL + 1, iF + 1, root_path), flush=True)
@@ -313,7 +329,11 @@ def run_data_list(flags, interp, device):
             warn("--png needs PIL, which is not importable: writing restored.npz only")
             png = False
     metrics = not flags.no_metrics
-    if metrics:
+    lpips = None
+    if metrics and flags.lpips_lin is not None:
+        from ebfi_amd.lpips import load_alex_lpips
+        lpips = load_alex_lpips(flags.lpips_lin, flags.lpips_backbone, device=device)
+    elif metrics:
         from ebfi_amd.metrics import LPIPS_UNAVAILABLE
         warn(LPIPS_UNAVAILABLE + "; psnr / ssim / mse only")
     frames, spent, results = 0, 0.0, []
@@ -321,7 +341,7 @@ def run_data_list(flags, interp, device):
         print("processing %s" % data_path, flush=True)
         n, s, r = infer_clip(interp, data_path, ds_cfg, os.path.join(flags.output_path, os.path.basename(data_path)), device,
                              seed=flags.data_seed + 100003 * k, png=png, metrics=metrics,
-                             info="inference %s on %s" % ([flags.model_path], data_path))
+                             info="inference %s on %s" % ([flags.model_path], data_path), lpips=lpips)
         frames, spent = frames + n, spent + s
         if r is not None:
             results.append((os.path.basename(data_path),) + r)
@@ -336,6 +356,12 @@ def run_data_list(flags, interp, device):
 @torch.no_grad()
 def main(argv=None):
     a = get_flags(argv)
+    if (a.lpips_lin is None) != (a.lpips_backbone is None):
+        raise SystemExit("infer_ours.py: LPIPS needs both weight files: --lpips_lin (the v0.1 alex.pth heads) and --lpips_backbone "
+                         "(torchvision's AlexNet state dict); got only %s" % ("--lpips_lin" if a.lpips_backbone is None else "--lpips_backbone"))
+    if a.lpips_lin is not None and (a.no_metrics or a.data_list is None):
+        warn("--lpips_lin / --lpips_backbone are unused: %s" % ("--no-metrics switches the scoring off" if a.no_metrics
+                                                                 else "only a --data_list run is scored"))
     torch.manual_seed(a.seed)
     device = torch.device(a.device)
     if device.type != "cuda":

@@ -19,8 +19,27 @@ class psnr_loss:
 
 
 class perceptual_loss:
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError(LPIPS_UNAVAILABLE)
+    """LPIPS (AlexNet, v0.1) on the device, from the two weight files named here: lin_path, the reference's
+    loss/PerceptualSimilarity/models/weights/v0.1/alex.pth, and backbone_path, torchvision's AlexNet state dict
+    (alexnet-owt-7be5be79.pth).  Without them it raises: no weight cache is searched."""
+
+    def __init__(self, weight=1.0, net='alex', use_gpu=True, gpu_ids=[0], lin_path=None, backbone_path=None):
+        if lin_path is None or backbone_path is None:
+            raise NotImplementedError(LPIPS_UNAVAILABLE)
+        from ebfi_amd.lpips import load_alex_lpips
+        self.model = load_alex_lpips(lin_path, backbone_path, device="cuda:%d" % gpu_ids[0], net=net)
+        self.weight = weight
+
+    def __call__(self, pred, target, normalize=True):
+        """pred, target: N x C x H x W; C == 1 and C == 3 in one call, any other C as the mean of per-channel calls, each channel
+        read as three (the reference's loop).  Returns weight * mean over N, a 0-dim device tensor."""
+        assert pred.size() == target.size()
+        c = pred.shape[1]
+        if c in (1, 3):
+            dist = self.model(pred, target, normalize=normalize)
+        else:
+            dist = sum(self.model(pred[:, i:i + 1], target[:, i:i + 1], normalize=normalize) for i in range(c)) / c
+        return self.weight * dist.mean()
 
 
 def _nchw(t):

@@ -37,6 +37,7 @@
  *   ebfi_events_to_stack        dataloader/encodings.py:307-350 (events_to_stack)
  *   ebfi_frame2lap / _frame2dcp myutils/utils.py:34-49 / :15-31
  *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
+ *   ebfi_lpips_*                perceptual_loss(net='alex') of the evaluation loop (loss/restore.py:10-40, LPIPS v0.1)
  */
 #ifndef EBFI_HIP_H
 #define EBFI_HIP_H
@@ -73,7 +74,8 @@ extern "C" {
  *  14  ebfi_to_c16_cat2 (the fp16 image of a two-part channel concatenation without the concatenated tensor); later, as a pure
  *      addition under the same number, ebfi_image_metrics_workspace / ebfi_image_metrics (evaluation PSNR / SSIM / MSE): no
  *      existing entry point changed, so a caller built against an earlier 14 header still calls every function it knows with
- *      the right arguments, and the binding's version check has nothing new to refuse */
+ *      the right arguments, and the binding's version check has nothing new to refuse; later still, as another pure addition
+ *      under 14, ebfi_lpips_params_bytes / _pack_params / _workspace / _alex (evaluation LPIPS, AlexNet v0.1) */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -630,6 +632,33 @@ int64_t ebfi_image_metrics_workspace(int64_t N, int C, int H, int W);
 int ebfi_image_metrics(const float *pred, const int64_t pred_strides[4], const float *target, const int64_t target_strides[4],
                        int64_t N, int C, int H, int W, float ssim_data_range, void *workspace, int64_t workspace_bytes,
                        float *out_psnr, float *out_ssim, float *out_mse, void *stream);
+
+/* ------------------------------------------------------------------ evaluation LPIPS (AlexNet, v0.1)
+ * Per pair n of an fp32 pred / target [N, C, H, W] (the evaluation loop's perceptual_loss(net='alex'), eval mode, spatial=False):
+ *   x'       = ((2x - 1) - shift_c) / scale_c with normalize != 0, (x - shift_c) / scale_c otherwise;
+ *              shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450); zero padding applies after it
+ *   f1 .. f5 = the five ReLU outputs of AlexNet's `features`: conv1 11x11/s4/p2 3->64, maxpool 3/s2, conv2 5x5/p2 64->192,
+ *              maxpool 3/s2, conv3 3x3/p1 192->384, conv4 3x3/p1 384->256, conv5 3x3/p1 256->256 (pools: no padding, floor
+ *              mode, NaN propagating)
+ *   d_l(p)   = sum_c w_lc (u0_c - u1_c)^2,  u = f / (sqrt(sum_c f_c^2) + 1e-10) of pred (u0) and target (u1)
+ *   lpips[n] = sum_l mean_p d_l(p);  out_layers[n][l] = mean_p d_l(p) (the reference's retPerLayer; may be NULL)
+ * C == 1 is read as three equal channels.  The convolutions run on exact fp32 MFMA; the per-pixel distances are summed in fp64
+ * in a fixed order.  A NaN or Inf anywhere in pair n's pred or target makes lpips[n] and its layers NaN, no other pair.
+ * Strides (elements, any int64) of N, C and rows; the column stride must be 1.
+ * ebfi_lpips_pack_params packs the five conv weights [Cout][Cin][k][k], biases [Cout] and head vectors [Cout] (the 1x1 heads
+ * lin{l}.model.1.weight) -- host arrays of 5 device pointers each, fp32 contiguous -- into `params` (16-byte aligned, at least
+ * ebfi_lpips_params_bytes() bytes), on `stream`.  workspace: 16-byte aligned, at least ebfi_lpips_workspace(N, C, H, W) bytes
+ * (pure host arithmetic; 0 for a bad shape): the five ReLU maps of all 2N images, tile partials and non-finite flags.
+ * Launches on `stream` only: no host synchronisation, no allocation, no atomics -- capturable, and bit-reproducible.
+ * Null pointers, C not in {1, 3}, H or W < 31 (AlexNet's trunk needs 31), a column stride other than 1 -> EBFI_ERR_ARG; a short
+ * workspace or params buffer -> EBFI_ERR_WORKSPACE; neither touches the GPU. */
+int64_t ebfi_lpips_params_bytes(void);
+int ebfi_lpips_pack_params(const float *const *conv_w, const float *const *conv_b, const float *const *lin_w, void *params,
+                           int64_t params_bytes, void *stream);
+int64_t ebfi_lpips_workspace(int64_t N, int C, int H, int W);
+int ebfi_lpips_alex(const float *pred, const int64_t pred_strides[4], const float *target, const int64_t target_strides[4],
+                    int64_t N, int C, int H, int W, int normalize, const void *params, void *workspace, int64_t workspace_bytes,
+                    float *out_lpips, float *out_layers, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
