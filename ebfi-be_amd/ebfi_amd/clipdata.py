@@ -330,6 +330,32 @@ def batches(dataset, batch_size, rank=0, world=1, seed=0, epochs=None, shuffle=T
         epoch += 1
 
 
+def shard_indices(n, rank, world):
+    """Indices of rank `rank` out of `n` items in order, as DistributedSampler(shuffle=False, drop_last=False) deals them: the
+    order is padded by wrapping around to ceil(n / world) * world entries and rank r takes every world-th one from r.  Every
+    rank gets the same count (so every rank makes the same number of collective calls over its shard) and the union covers
+    every index; n = 0 gives no items on any rank."""
+    n, rank, world = int(n), int(rank), int(world)
+    if not 0 <= rank < world:
+        raise ValueError("rank %d outside world %d" % (rank, world))
+    if n <= 0:
+        return []
+    per = -(-n // world)
+    return [(rank + k * world) % n for k in range(per)]
+
+
+def eval_batches(dataset, batch_size, rank=0, world=1, seed=0, drop_last=False):
+    """One pass over `dataset` in file order for validation (the reference's valid_dataloader: no shuffle, DistributedSampler
+    shards, h5dataloader.py:47-57): this rank's `shard_indices` in batches of `batch_size`; yields collated dicts [B, L=1, ...].
+    The item seeds depend on the index only, so every pass produces the same tensors."""
+    order = shard_indices(len(dataset), rank, world)
+    for k in range(0, len(order), batch_size):
+        idx = order[k:k + batch_size]
+        if len(idx) < batch_size and drop_last:
+            break
+        yield collate([dataset.__getitem__(i, seed=seed + i) for i in idx])
+
+
 def model_inputs(batch):
     """The reference's loop over one collated batch (train_ours.py:226-251, L = NumP = 1): yields
     (Frame [B,3,H,W], Event [B,TB,2,H,W], T [B,1], GTEx [B,1], LatentF [B,3,H,W]) per latent frame."""

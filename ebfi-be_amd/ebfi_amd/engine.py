@@ -68,6 +68,19 @@ def synthetic_batch_from_raw_events(B, H, W, TB=16, device="cuda", seed=123, ran
     return frame, torch.stack(stacks).contiguous(), t, gtex, target
 
 
+def synthetic_validation_batch(B, H, W, TB=16, num_frames=4, device="cuda", seed=0):
+    """A period for `Engine.validate` with the statistics of `synthetic_batch`: (Frame, Event, Ts [B, NumF] = k / NumF like the
+    dataset's RelativeLatentTs, GTEx, LatentF [B, NumF, 3, H, W]).  Always drawn on the host from ONE generator seeded with
+    `seed`: the same tensors on every machine and at every validation stamp."""
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    frame = torch.rand(B, 3, H, W, generator=g)
+    event = torch.poisson(torch.full((B, TB, 2, H, W), 0.35), generator=g)
+    gtex = torch.rand(B, 1, generator=g) * 0.4 + 0.55
+    latent = torch.rand(B, num_frames, 3, H, W, generator=g)
+    ts = (torch.arange(num_frames) / num_frames).expand(B, num_frames).contiguous()
+    return tuple(v.to(device) for v in (frame, event, ts, gtex, latent))
+
+
 class Engine:
     def __init__(self, model_args=None, device="cuda", precision="fp32", lr=1e-4, seed=None, train=True, graph=False,
                  accu_step=1, betas=(0.9, 0.999), backward_f16=None, forward_f16="filters", strict_graph=None):
@@ -310,6 +323,65 @@ class Engine:
     def infer(self, frame, event, t, gtex=None):
         with self._autocast(), self._bank():
             return self.model(frame, event, t, gtex)[-1]
+
+    VALID_KEYS = ("valid_loss", "valid_psnr", "valid_ssim")
+
+    def validator(self, group=None):
+        """The ClipInterpolator validation runs through, built once per `group` over the engine's OWN model in the engine's
+        precision (prefix once per batch, grouped timestamps, graph replay).  It keeps its own weight bank and scale book: the
+        training bank, the training ScaleBook and the captured training graphs are never touched by a validation pass."""
+        cache = self.__dict__.setdefault("_validators", {})
+        if group not in cache:
+            cache[group] = ClipInterpolator(self.model, precision=self.precision, graph=self.device.type == "cuda", hoist=True,
+                                            group=group)
+        return cache[group]
+
+    @torch.no_grad()
+    def validate(self, batch, load=0, group=None, refresh=True, eps=1e-3):
+        """One (batch, load) of the reference's validation loop (train_ours.py:566-591) -> {"valid_loss", "valid_psnr",
+        "valid_ssim"}: 0-dim float64 DEVICE tensors.
+          valid_loss  sum_i CharbonnierLoss(Final_i, LatentF_i) / NumI, the loss a SUM over the whole batch -- the reference's
+                      value, NOT a per-pixel mean: it scales with batch and crop size
+          valid_psnr  mean over the B * NumI frames of ebfi_amd.metrics.frame_metrics (-psnr is the score the reference left
+                      commented out at :587)
+          valid_ssim  likewise, SSIM
+        batch: a collated ebfi_amd.clipdata batch (dict, [B, L, ...]; `load` picks the load) or the tuple
+        (Frame [B,3,H,W], Event [B,TB,2,H,W], Ts [B,NumF], GTEx [B,1], LatentF [B,NumF,3,H,W]).
+        refresh: re-pack the validator's weight images from the current parameters first (and retake its captured graph).  The native Adam step writes the
+        flat parameter buffer through a raw pointer, which moves no tensor version counter, so the validator's bank cannot see
+        an optimiser step by itself: pass True (the default) at least for the first batch of every validation pass.
+        Nothing is read back to the host here; the training state (module modes, compute dtype, active bank / book, scale
+        book, graphs, gradients, accumulation window) is left as found."""
+        from .loss import charbonnier_per_sample
+        from .metrics import frame_metrics
+        if isinstance(batch, dict):
+            latent = batch["SeqLatentF"][:, load]
+            latent = latent.reshape((latent.shape[0], -1) + tuple(latent.shape[-3:]))        # [B, NumP * NumF, 3, H, W]
+            frame = batch["SeqBlurryF"][:, load, 0]
+            event = batch["SeqHREv"][:, load]
+            ts = batch["RelativeLatentTs"][:, load, 0]
+            gtex = batch["SeqExposureDuty"][:, load, 0]
+        else:
+            frame, event, ts, gtex, latent = batch
+        frame, event, gtex = frame.contiguous(), event.contiguous(), None if gtex is None else gtex.contiguous()
+        B, num_i = int(ts.shape[0]), int(ts.shape[-1])
+        if latent.dim() != 5 or latent.shape[0] != B or latent.shape[1] != num_i:
+            raise ValueError("validate: LatentF %s does not match Ts %s" % (tuple(latent.shape), tuple(ts.shape)))
+        interp = self.validator(group)
+        if refresh:
+            interp.refresh_weights()
+            # ... and retake the per-timestamp graph under the new weights (one warm-up pass and one capture per pass and input
+            # shape): a graph captured under earlier weights replays to within 1.1e-6 of the frames a fresh capture or the eager
+            # launches give (measured after three optimiser steps), not bit-identically, and a validation score must not depend
+            # on when the validator was first used
+            interp._captured.clear()
+        final = interp(frame, event, gtex, [ts[:, i] for i in range(num_i)])                  # [B, NumI, 3, H, W]
+        pred = final.reshape((B * num_i,) + tuple(final.shape[2:])).float()
+        target = latent.reshape((B * num_i,) + tuple(latent.shape[2:])).float()
+        loss = charbonnier_per_sample(pred, target, eps).double().sum() / num_i
+        psnr, ssim, _ = frame_metrics(pred, target)
+        values = torch.stack([loss, psnr.double().mean(), ssim.double().mean()])
+        return {k: values[i] for i, k in enumerate(self.VALID_KEYS)}
 
 
 class ClipInterpolator:

@@ -221,3 +221,96 @@ class TrainLoss(nn.Module):
         if sharp_pre is None:
             return term(sharp) / accu_step
         return (c_sharp * term(sharp) + c_pre * term(sharp_pre)) / accu_step
+
+
+# ------------------------------------------------------------------------------------------------ Charbonnier (validation)
+_cb_workspaces = {}
+
+
+def _cb_workspace(device, stream, shape):
+    key = (device, stream, shape)
+    ws = _cb_workspaces.get(key)
+    if ws is None:
+        nbytes = N.lib().ebfi_charbonnier_workspace(*shape)
+        ws = torch.empty(max(nbytes // 8, 2), dtype=torch.float64, device=device)   # (float64: 16-byte aligned storage)
+        _cb_workspaces[key] = ws
+    return ws
+
+
+def _cb_check(x, y, eps):
+    N.require_gpu(x, y)
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError("Charbonnier loss takes two [N, C, H, W] tensors of one shape, got %s and %s"
+                         % (tuple(x.shape), tuple(y.shape)))
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError("Charbonnier loss takes float32 tensors, got %s / %s" % (x.dtype, y.dtype))
+    if x.device != y.device:
+        raise ValueError("x on %s, y on %s" % (x.device, y.device))
+    if not eps > 0:
+        raise ValueError("eps must be positive, got %r" % (eps,))
+    # the kernels read rows through arbitrary strides but need unit column stride
+    x = x if x.stride(3) == 1 or x.shape[3] == 1 else x.contiguous()
+    y = y if y.stride(3) == 1 or y.shape[3] == 1 else y.contiguous()
+    return x, y
+
+
+def _cb_strides(t):
+    return N.i64x4(tuple(t.stride())[:3] + (1,))
+
+
+def _cb_forward(x, y, eps):
+    n, c, h, w = (int(v) for v in x.shape)
+    out = torch.empty(n, dtype=torch.float32, device=x.device)
+    if n == 0 or c * h * w == 0:
+        return out.zero_()
+    with torch.cuda.device_of(x):
+        stream = N.stream_ptr(x.device)
+        ws = _cb_workspace(x.device, stream.value, (n, c, h, w))
+        rc = N.lib().ebfi_charbonnier_forward(N.ptr(x), _cb_strides(x), N.ptr(y), _cb_strides(y), n, c, h, w, float(eps),
+                                              N.ptr(ws), ws.numel() * 8, N.ptr(out), stream)
+    N.check(rc, "ebfi_charbonnier_forward")
+    return out
+
+
+@torch.no_grad()
+def charbonnier_per_sample(x, y, eps=1e-3):
+    """[N] float32 device tensor: sum over C, H, W of sqrt((x - y)^2 + eps) per sample of an fp32 pair [N, C, H, W] (tensors or
+    strided views with unit column stride).  No autograd; two launches on the current stream, nothing is copied back."""
+    x, y = _cb_check(x, y, eps)
+    return _cb_forward(x, y, eps)
+
+
+class _Charbonnier(torch.autograd.Function):
+    """sum(sqrt((x - y)^2 + eps)) on the kernel pair of csrc/charbonnier.hip."""
+
+    @staticmethod
+    def forward(ctx, x, y, eps):
+        ctx.eps = float(eps)
+        ctx.save_for_backward(x, y)
+        return _cb_forward(x, y, eps).sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        n, c, h, w = (int(v) for v in x.shape)
+        g = g.contiguous().float().reshape(1)
+        gx = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+        if gx.numel():
+            with torch.cuda.device_of(x):
+                rc = N.lib().ebfi_charbonnier_backward(N.ptr(x), _cb_strides(x), N.ptr(y), _cb_strides(y), n, c, h, w, ctx.eps,
+                                                       N.ptr(g), N.ptr(gx), N.stream_ptr(x.device))
+            N.check(rc, "ebfi_charbonnier_backward")
+        return (gx if ctx.needs_input_grad[0] else None), (-gx if ctx.needs_input_grad[1] else None), None
+
+
+class CharbonnierLoss(nn.Module):
+    """Charbonnier loss with the reference's call contract (loss/restore.py:95-105): forward(x, y) -> 0-dim tensor,
+    sum(sqrt((x - y)^2 + eps)) over ALL elements (a sum, not a mean; eps under the root).  Device tensors only."""
+
+    def __init__(self, eps=1e-3):
+        super().__init__()
+        self.eps = eps
+
+    def forward(self, x, y):
+        x, y = _cb_check(x, y, self.eps)
+        return _Charbonnier.apply(x, y, self.eps)

@@ -1,5 +1,7 @@
 """Drop-in for the evaluation metrics of `loss.restore` (loss/restore.py:13-92): the reference's call contract -- a 1 x C x H x W
-pair in, a Python float out -- computed by ebfi_amd.metrics on the device instead of scikit-image on the host."""
+pair in, a Python float out -- computed by ebfi_amd.metrics on the device instead of scikit-image on the host.  CharbonnierLoss (loss/restore.py:95-105, the
+validation score of the trainer) is the device implementation of ebfi_amd.loss."""
+from ebfi_amd.loss import CharbonnierLoss  # noqa: F401
 from ebfi_amd.metrics import LPIPS_UNAVAILABLE, frame_metrics
 
 

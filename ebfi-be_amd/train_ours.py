@@ -12,13 +12,19 @@ trainer:{training_mode, iteration, monitor_best}} (train_ours.py:621-671) with -
 _resume_checkpoint (:673-716): training continues at trainer.iteration + 1.
 Unlike the reference (whose fwd+bwd sits inside model.no_sync()) gradients ARE averaged across ranks every optimiser
 step (one flat RCCL all-reduce).  Data: synthetic batches or, with --data, recorded clips through
-ebfi_amd.clipdata (the tensor contract of dataloader/h5dataset.py:283-295 from .npz clips, or .h5 when h5py is installed);
-TensorBoard, validation and early stopping of the reference are out of scope.
+ebfi_amd.clipdata (the tensor contract of dataloader/h5dataset.py:283-295 from .npz clips, or .h5 when h5py is installed).
+Validation (trainer.do_validation, off unless the config switches it on) follows the reference's :309-333 / :392-435 / :545-619:
+every valid_step-th iteration Engine.validate scores the validation set (valid_loss = the reference's Charbonnier sum,
+valid_psnr, valid_ssim; recorded clips of valid_dataloader / --valid-data, or a fixed set of synthetic batches), `Monitor`
+takes the best / early-stop decision of eval_model_performance, a best stamp writes checkpoint-iteration{it}.pth AND
+model_best_until_iteration{it}.pth, and trainer.monitor_best travels through --resume.  Unlike the reference, every rank
+holds the rank-averaged values and takes the same decision.  TensorBoard and image dumps of the reference are out of scope.
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train_ours.py -c config/train_ours.yml -id run
     python train_ours.py -c config/train_ours.yml -id run --iterations 20
 """
 import argparse
+import math
 import os
 import sys
 import time
@@ -80,6 +86,78 @@ def trainer_settings(config, cli_iterations=None):
             "log_step": max(1, int(get("train_log_step", 10)))}
 
 
+def validation_settings(config, cli_valid_data=None):
+    """The reference's validation keys (train_ours.yml:86-100, :151-192); every absent key means OFF / the reference's default.
+    valid_data: --valid-data, else valid_dataloader.path_to_datalist_txt; None -> `valid_batches` fixed synthetic batches."""
+    tr = config.get("trainer", {}) or {}
+    ib = tr.get("iteration_based_train", {}) or {}
+    vd = config.get("valid_dataloader") or {}
+    get = lambda k, d: ib.get(k, tr.get(k, d))
+    early = tr.get("early_stop", math.inf)
+    return {"do_validation": bool(tr.get("do_validation", False)),
+            "valid_step": max(1, int(float(get("valid_step", 5000)))),
+            "valid_log_step": max(1, int(float(get("valid_log_step", 50)))),
+            "monitor": str(tr.get("monitor", "off")),
+            "early_stop": math.inf if early is None else float(early),
+            "valid_batches": max(1, int(tr.get("valid_batches", 2))),
+            "valid_data": cli_valid_data or vd.get("path_to_datalist_txt"),
+            "batch_size": None if vd.get("batch_size") is None else int(vd["batch_size"]),
+            "drop_last": bool(vd.get("drop_last", False)),
+            "dataset": vd.get("dataset") or {}}
+
+
+class Monitor:
+    """eval_model_performance of the reference (train_ours.py:155-163, :392-435), host-only.  monitor: 'off' or '<min|max> <key>'.
+    `evaluate(log)` -> (stop_training, best): improved means <= / >= the best so far (a tie counts), a missing key warns and
+    leaves every counter alone, training stops once not_improved_count > early_stop.  `best` starts at +inf / -inf; with
+    monitor 'off' it is None and evaluate never reports a best or a stop (checkpoints then carry monitor_best None)."""
+
+    def __init__(self, monitor="off", early_stop=math.inf, warn=None):
+        self.monitor = monitor or "off"
+        self.warn = warn or (lambda msg: print(msg, file=sys.stderr, flush=True))
+        self.not_improved_count = 0
+        if self.monitor == "off":
+            self.mode, self.metric, self.best, self.early_stop = "off", None, None, math.inf
+            return
+        parts = self.monitor.split()
+        if len(parts) != 2 or parts[0] not in ("min", "max"):
+            raise ValueError("trainer.monitor must be 'off' or '<min|max> <key>', got %r" % (monitor,))
+        self.mode, self.metric = parts
+        self.best = math.inf if self.mode == "min" else -math.inf
+        self.early_stop = math.inf if early_stop is None else float(early_stop)
+
+    def evaluate(self, log):
+        if self.mode == "off":
+            return False, False
+        best = False
+        if self.metric not in log:
+            self.warn("Warning: Metric '%s' is not found. Ignore this stamp where using this metric to monitor." % self.metric)
+        else:
+            value = log[self.metric]
+            if (self.mode == "min" and value <= self.best) or (self.mode == "max" and value >= self.best):
+                self.best, self.not_improved_count, best = value, 0, True
+            else:
+                self.not_improved_count += 1
+        return self.not_improved_count > self.early_stop, best
+
+    def stop_message(self):
+        return "Validation performance didn't improve for %s stamps. Training stops." % _fmt_count(self.early_stop)
+
+
+def _fmt_count(v):
+    return "%d" % v if math.isfinite(v) and float(v).is_integer() else "%s" % v
+
+
+def validation_seeds(seed, count):
+    """Seeds of the synthetic validation batches: seed - 1, seed - 2, ...  Every training batch is drawn from
+    seed + 1000 * pass + rank >= seed (main loop), so the two sets cannot meet."""
+    return [int(seed) - 1 - j for j in range(int(count))]
+
+
+def best_checkpoint_name(iteration):
+    return "model_best_until_iteration%d.pth" % int(iteration)      # train_ours.py:669
+
+
 def checkpoint_state(eng, scheduler, config, iteration, monitor_best=None):
     """The reference's checkpoint dict (train_ours.py:628-655), key for key; `iteration` = index of the last completed
     optimiser step, resumed at +1 (:695)."""
@@ -91,16 +169,24 @@ def checkpoint_state(eng, scheduler, config, iteration, monitor_best=None):
             "trainer": {"training_mode": TRAINING_MODE, "iteration": int(iteration), "monitor_best": monitor_best}}
 
 
-def save_checkpoint(path, eng, scheduler, config, iteration):
+def save_checkpoint(path, eng, scheduler, config, iteration, monitor_best=None, save_best=False):
+    """checkpoint-iteration{it}.pth at `path`; save_best: the same state again as model_best_until_iteration{it}.pth beside it
+    (train_ours.py:665-671).  Returns the paths written."""
     os.makedirs(os.path.dirname(path), exist_ok=True)
-    torch.save(checkpoint_state(eng, scheduler, config, iteration), path)
+    state = checkpoint_state(eng, scheduler, config, iteration, monitor_best)
+    paths = [path] + ([os.path.join(os.path.dirname(path), best_checkpoint_name(iteration))] if save_best else [])
+    for p in paths:
+        torch.save(state, p)
+    return paths
 
 
-def resume_checkpoint(path, eng, scheduler, config, reset=False, map_location="cpu"):
+def resume_checkpoint(path, eng, scheduler, config, reset=False, map_location="cpu", monitor=None):
     """Resumer + _resume_checkpoint of the reference (myutils/utils.py:178-215, train_ours.py:673-716): optimiser and
     scheduler states are restored only without --reset and when the training mode matches, each only when the configured
-    name equals the checkpoint's; the model is always loaded (strict=False) when its name matches.  Returns the first
-    iteration to run."""
+    name equals the checkpoint's; the model is always loaded (strict=False) when its name matches.  monitor: a Monitor whose
+    `best` is restored from trainer.monitor_best under the same condition as the optimiser state (:696; a checkpoint written
+    without validation carries None and leaves it alone); its not_improved_count restarts at 0.  Returns the first iteration
+    to run."""
     cpt = torch.load(path, map_location=map_location, weights_only=False)
     start = 0
     tr = cpt["trainer"]
@@ -112,6 +198,8 @@ def resume_checkpoint(path, eng, scheduler, config, reset=False, map_location="c
             for group, lr in zip(eng.optimizer.param_groups, scheduler.get_last_lr()):
                 group["lr"] = lr
         start = int(tr["iteration"]) + 1
+        if monitor is not None and monitor.mode != "off" and tr.get("monitor_best") is not None:
+            monitor.best = tr["monitor_best"]
     if config["model"]["name"] == cpt["model"]["name"]:
         eng.model.load_state_dict(cpt["model"]["states"], strict=False)
     eng.iteration = start
@@ -134,6 +222,48 @@ def real_data_passes(path, config, B, TB, device, rank, world, seed):
     for batch in clipdata.batches(ds, B, rank=rank, world=world, seed=seed):
         for inputs in clipdata.model_inputs(batch):
             yield inputs
+
+
+def validation_batches(vs, config, args, B, H, W, TB, device, rank, world):
+    """-> a function that yields this rank's validation batches, the same ones at every stamp, sharded so that every rank gets
+    the same count (clipdata.shard_indices).  Recorded clips go through clipdata with the valid_dataloader.dataset section
+    (reference keys); without a path: `valid_batches` synthetic periods, made once and kept on the device."""
+    from ebfi_amd import clipdata
+    from ebfi_amd.engine import synthetic_validation_batch
+    ds_cfg = vs["dataset"]
+    vb = vs["batch_size"] or B
+    if vs["valid_data"]:
+        ds = clipdata.ClipDataset(vs["valid_data"], time_bins=int(ds_cfg.get("time_bins", TB)),
+                                  frames_per_period=int(ds_cfg.get("NumFramePerPeriod", 16)),
+                                  frames_per_blurry=int(ds_cfg.get("NumFramePerBlurry", 16)),
+                                  exposure_method=ds_cfg.get("ExposureMethod", "Custom"),
+                                  exposure_time=ds_cfg.get("ExposureTime", [9, 10, 11, 12, 13, 14, 15]),
+                                  device=device, seed=args.seed, **clipdata.dataset_args_from_config(ds_cfg))
+        if len(ds) == 0:
+            raise SystemExit("--valid-data: no complete period in %s" % vs["valid_data"])
+        return lambda: clipdata.eval_batches(ds, vb, rank=rank, world=world, seed=args.seed, drop_last=vs["drop_last"])
+    seeds = validation_seeds(args.seed, vs["valid_batches"])
+    num_f = int(ds_cfg.get("NumFramePerPeriod", 4))
+    mine = [synthetic_validation_batch(vb, H, W, TB, num_f, device=device, seed=seeds[j])
+            for j in clipdata.shard_indices(len(seeds), rank, world)]
+    return lambda: iter(mine)
+
+
+def run_validation(eng, batches, tracker, stamp, log_step=50, rank=0):
+    """_valid of the reference (train_ours.py:545-619) for one stamp: every (batch, load) is scored by Engine.validate, averaged
+    over ranks (reduce_tensor: ONE collective and ONE host read per (batch, load), none per timestamp) and averaged over the
+    stamp by the MetricTracker.  Every rank feeds its tracker with the same reduced values.  Returns tracker.result()."""
+    tracker.reset()
+    for k, batch in enumerate(batches()):
+        loads = batch["SeqLatentF"].shape[1] if isinstance(batch, dict) else 1
+        for load in range(loads):
+            vals = eng.validate(batch, load=load, refresh=(k == 0 and load == 0))      # weights re-packed once per pass
+            host = reduce_tensor(torch.stack([vals[key] for key in eng.VALID_KEYS])).tolist()
+            for key, v in zip(eng.VALID_KEYS, host):
+                tracker.update(key, v)
+            if rank == 0 and k % log_step == 0:
+                print("Valid timestamp: %d [batch %d] valid_loss: %.4e" % (stamp, k, host[0]), flush=True)
+    return tracker.result()
 
 
 def main():
@@ -160,6 +290,9 @@ def main():
                     help="recorded clips instead of synthetic batches: a directory of .npz clips (or .h5 in the reference's layout "
                          "when h5py is installed), a datalist .txt, or one clip file (ebfi_amd.clipdata); the dataset section of "
                          "the config (train_dataloader.dataset, reference keys) sets periods / exposure / crop")
+    ap.add_argument("--valid-data", default=None,
+                    help="validation clips (same forms as --data) instead of valid_dataloader.path_to_datalist_txt; used when "
+                         "trainer.do_validation is on (without either: a fixed set of trainer.valid_batches synthetic batches)")
     ap.add_argument("--raw-events", action="store_true",
                     help="build the event tensor from synthetic raw event lists with the device events_to_stack kernel "
                          "(the reference's data path, h5dataset.py:327-352) instead of drawing voxel counts directly")
@@ -168,6 +301,7 @@ def main():
         config = yaml.safe_load(fh)
     tr = config.get("trainer", {}) or {}
     st = trainer_settings(config, args.iterations)
+    vs = validation_settings(config, args.valid_data)
     rank, world, gpu = init_distributed_mode()
     device = torch.device("cuda", gpu)
     assert config["model"]["name"] == "EVFIAutoEx", "only the EVFIAutoEx hot path is implemented"
@@ -179,7 +313,11 @@ def main():
                  graph=args.graph or bool(tr.get("graph", False)), accu_step=st["accu_step"],
                  backward_f16=False if args.no_f16_backward else None, forward_f16=None if args.no_f16_forward else "filters")
     scheduler = build_lr_scheduler(config, eng.optimizer.inner)
-    start = resume_checkpoint(args.resume, eng, scheduler, config, reset=args.reset, map_location=device) if args.resume else 0
+    # monitor / best checkpoint / early stop (train_ours.py:155-163): only with validation on -- otherwise monitor_best stays None
+    monitor = Monitor(vs["monitor"], vs["early_stop"],
+                      warn=None if rank == 0 else (lambda msg: None)) if vs["do_validation"] else None
+    start = resume_checkpoint(args.resume, eng, scheduler, config, reset=args.reset, map_location=device,
+                              monitor=monitor) if args.resume else 0
     B, H, W = int(tr.get("batch_size", 8)), int(tr.get("height", 256)), int(tr.get("width", 256))
     TB = int(config["model"]["args"]["TB"])
     out_dir = os.path.join(tr.get("output_path", "./output"), "models", config.get("experiment", "Ours"), args.runid)
@@ -190,6 +328,11 @@ def main():
     t0, frames, it = None, 0, start
     make = synthetic_batch_from_raw_events if args.raw_events else synthetic_batch
     real = real_data_passes(args.data, config, B, TB, device, rank, world, args.seed) if args.data else None
+    valid_stamp, valid_batches, tracker = 1, None, None
+    if vs["do_validation"]:
+        from ebfi_amd.metrics import MetricTracker
+        valid_batches = validation_batches(vs, config, args, B, H, W, TB, device, rank, world)
+        tracker = MetricTracker(eng.VALID_KEYS)
     while it < st["iterations"]:
         for micro in range(st["accu_step"]):
             if real is not None:
@@ -215,19 +358,37 @@ def main():
         if t0 is None and eng.settled:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-        # periodic checkpoints as train_ours.py:331-333 (saved BEFORE this iteration's scheduler step, like there), plus one
-        # after the last iteration
-        if rank == 0 and ((st["save_period"] and it % st["save_period"] == 0 and it != 0) or it == st["iterations"] - 1):
+        # validation every valid_step-th iteration, never at 0 (train_ours.py:309-328); all ranks take part and decide alike
+        best = stop = False
+        if vs["do_validation"] and it % vs["valid_step"] == 0 and it != 0:
+            t_valid = time.perf_counter()
+            val_log = run_validation(eng, valid_batches, tracker, valid_stamp, vs["valid_log_step"], rank)
+            if t0 is not None:           # (the logged rate is the training rate: the stamp's time is taken off the clock)
+                t0 += time.perf_counter() - t_valid
+            stop, best = monitor.evaluate(val_log)
+            if rank == 0:
+                print("Valid stamp: %d %s (best %r)" % (valid_stamp, " ".join("%s: %.6e" % (k, val_log[k]) for k in eng.VALID_KEYS),
+                                                        monitor.best), flush=True)
+                if stop:
+                    print(monitor.stop_message(), flush=True)
+            valid_stamp += 1
+        # periodic checkpoints as train_ours.py:331-333 (saved BEFORE this iteration's scheduler step, like there; also when this
+        # stamp is the best so far, then twice: :665-671), plus one after the last iteration -- the one an early stop ends at too
+        if rank == 0 and ((st["save_period"] and it % st["save_period"] == 0 and it != 0) or best or stop
+                          or it == st["iterations"] - 1):
             path = os.path.join(out_dir, "checkpoint-iteration%d.pth" % it)
-            save_checkpoint(path, eng, scheduler, config, it)
-            print("saved", path, flush=True)
+            for p in save_checkpoint(path, eng, scheduler, config, it, monitor.best if monitor is not None else None, best):
+                print("saved", p, flush=True)
+        if stop:
+            it += 1
+            break
         if scheduler is not None and it % st["lr_change_rate"] == 0 and it != 0 and lr_now >= st["lr_min"]:   # :335-338
             scheduler.step()
         it += 1
     if rank == 0 and eng.book is not None:
         # fp16 backward (ebfi_amd.f16scale): optimiser steps skipped because an operand left the fp16 range (expected: 0)
         print("fp16 backward: %d of %d optimiser steps skipped by the overflow guard, %d operand scale slots"
-              % (eng.book.skipped_steps(), st["iterations"] - start, len(eng.book.index)), flush=True)
+              % (eng.book.skipped_steps(), it - start, len(eng.book.index)), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

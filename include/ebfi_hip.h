@@ -38,6 +38,7 @@
  *   ebfi_frame2lap / _frame2dcp myutils/utils.py:34-49 / :15-31
  *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
  *   ebfi_lpips_*                perceptual_loss(net='alex') of the evaluation loop (loss/restore.py:10-40, LPIPS v0.1)
+ *   ebfi_charbonnier_*          CharbonnierLoss of the validation loop (loss/restore.py:95-105, train_ours.py:588)
  */
 #ifndef EBFI_HIP_H
 #define EBFI_HIP_H
@@ -75,7 +76,8 @@ extern "C" {
  *      addition under the same number, ebfi_image_metrics_workspace / ebfi_image_metrics (evaluation PSNR / SSIM / MSE): no
  *      existing entry point changed, so a caller built against an earlier 14 header still calls every function it knows with
  *      the right arguments, and the binding's version check has nothing new to refuse; later still, as another pure addition
- *      under 14, ebfi_lpips_params_bytes / _pack_params / _workspace / _alex (evaluation LPIPS, AlexNet v0.1) */
+ *      under 14, ebfi_lpips_params_bytes / _pack_params / _workspace / _alex (evaluation LPIPS, AlexNet v0.1); and, again as a
+ *      pure addition under 14, ebfi_charbonnier_workspace / _forward / _backward (the validation loop's Charbonnier loss) */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -659,6 +661,28 @@ int64_t ebfi_lpips_workspace(int64_t N, int C, int H, int W);
 int ebfi_lpips_alex(const float *pred, const int64_t pred_strides[4], const float *target, const int64_t target_strides[4],
                     int64_t N, int C, int H, int W, int normalize, const void *params, void *workspace, int64_t workspace_bytes,
                     float *out_lpips, float *out_layers, void *stream);
+
+/* ------------------------------------------------------------------ Charbonnier loss (validation)
+ * CharbonnierLoss of the reference (loss/restore.py:95-105; the validation score of train_ours.py:588) per sample n of an fp32
+ * pair x / y [N, C, H, W]:
+ *   out[n] = sum over c, h, w of sqrt((x - y)^2 + eps)        -- a SUM, not a mean; eps sits under the root and is not squared
+ * (the reference's scalar is the sum of out over n).  Every term is formed in fp32 (subtract, fused multiply-add, root) and
+ * accumulated in fp64; out[n] is rounded to fp32 once.  A NaN or inf element makes out[n] non-finite: nothing is dropped.
+ * Strides (elements, any int64) of N, C and rows; the column stride must be 1 (EBFI_ERR_UNSUPPORTED otherwise).  16-byte loads
+ * when both base pointers are 16-byte aligned and all strides are multiples of 4, scalar loads otherwise.
+ * Forward: two launches on `stream` (one fp64 partial per tile into `workspace`, then a fixed-order fp64 reduction per sample):
+ * no host synchronisation, no allocation, no atomics -- capturable, and bit-reproducible.  A tile is R = ceil(4096 / W)
+ * consecutive rows of a sample's C * H rows; workspace: 16-byte aligned, at least ebfi_charbonnier_workspace(N, C, H, W) =
+ * N * ceil(C * H / R) * 8 bytes (pure host arithmetic; 0 for a bad shape).  out: device float[N].
+ * Backward: grad_x[n,c,h,w] = g[0] * (x - y) / sqrt((x - y)^2 + eps), g a device scalar (the gradient with respect to y is
+ * its negative), written to a CONTIGUOUS [N, C, H, W] tensor in one streaming launch.
+ * Null pointers, N < 0, C / H / W < 1, eps not positive and finite, a misaligned workspace -> EBFI_ERR_ARG; a column stride
+ * other than 1 -> EBFI_ERR_UNSUPPORTED; a short workspace -> EBFI_ERR_WORKSPACE; none of them touches the GPU. */
+int64_t ebfi_charbonnier_workspace(int64_t N, int C, int H, int W);
+int ebfi_charbonnier_forward(const float *x, const int64_t x_strides[4], const float *y, const int64_t y_strides[4], int64_t N,
+                             int C, int H, int W, float eps, void *workspace, int64_t workspace_bytes, float *out, void *stream);
+int ebfi_charbonnier_backward(const float *x, const int64_t x_strides[4], const float *y, const int64_t y_strides[4], int64_t N,
+                              int C, int H, int W, float eps, const float *g, float *grad_x, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
