@@ -314,3 +314,97 @@ class CharbonnierLoss(nn.Module):
     def forward(self, x, y):
         x, y = _cb_check(x, y, self.eps)
         return _Charbonnier.apply(x, y, self.eps)
+
+
+# ------------------------------------------------------------------------------------------------ duty head + MSE (stage 1)
+_dh_workspaces = {}
+
+
+def _dh_workspace(device, stream, shape):
+    key = (device, stream, shape)
+    ws = _dh_workspaces.get(key)
+    if ws is None:
+        nbytes = N.lib().ebfi_duty_head_workspace(*shape)
+        ws = torch.empty(max(nbytes // 8, 2), dtype=torch.float64, device=device)   # (float64: 16-byte aligned storage)
+        _dh_workspaces[key] = ws
+    return ws
+
+
+def _dh_check(ex, duty):
+    N.require_gpu(ex, duty)
+    if ex.dim() != 4 or ex.shape[1] != 1:
+        raise ValueError("the duty head takes a [B, 1, H, W] map, got %s" % (tuple(ex.shape),))
+    if ex.dtype != torch.float32:
+        raise ValueError("the duty head takes a float32 map, got %s" % ex.dtype)
+    if ex.shape[0] == 0 or ex.shape[2] * ex.shape[3] == 0:
+        raise ValueError("the duty head needs a non-empty map, got %s" % (tuple(ex.shape),))
+    if duty is not None:
+        if duty.numel() != ex.shape[0] or duty.dtype != torch.float32 or duty.device != ex.device:
+            raise ValueError("duty must be a float32 [B, 1] tensor on the map's device, got %s %s on %s for B = %d"
+                             % (duty.dtype, tuple(duty.shape), duty.device, ex.shape[0]))
+        duty = duty.detach().reshape(-1).contiguous()
+    # rows are read through arbitrary strides, columns need unit stride
+    return (ex if ex.stride(3) == 1 or ex.shape[3] == 1 else ex.contiguous()), duty
+
+
+def _dh_forward(ex, duty, scale):
+    b, _, h, w = (int(v) for v in ex.shape)
+    Ex = torch.empty((b, 1), dtype=torch.float32, device=ex.device)
+    loss = torch.empty((), dtype=torch.float32, device=ex.device) if duty is not None else None
+    with torch.cuda.device_of(ex):
+        stream = N.stream_ptr(ex.device)
+        ws = _dh_workspace(ex.device, stream.value, (b, h, w))
+        rc = N.lib().ebfi_duty_head_forward(N.ptr(ex), N.i64x4(tuple(ex.stride())[:3] + (1,)), N.ptr(duty), b, h, w, float(scale),
+                                            N.ptr(ws), ws.numel() * 8, N.ptr(Ex), N.ptr(loss), stream)
+    N.check(rc, "ebfi_duty_head_forward")
+    return Ex, loss
+
+
+@torch.no_grad()
+def duty_head(ex):
+    """Ex [B, 1] = sigmoid(mean over H, W) of an fp32 map [B, 1, H, W] (the tail of ExposureDecision.forward, reference
+    model_singleframe.py:75-76) on the kernels of csrc/dutyhead.hip.  No autograd; two launches, nothing is copied back."""
+    ex, _ = _dh_check(ex, None)
+    return _dh_forward(ex, None, 1.0)[0]
+
+
+class _DutyMSE(torch.autograd.Function):
+    """(scale * MSELoss(sigmoid(mean(ex)), duty), Ex) on the kernels of csrc/dutyhead.hip; Ex is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, ex, duty, scale):
+        Ex, loss = _dh_forward(ex, duty, scale)
+        ctx.scale, ctx.shape = float(scale), tuple(int(v) for v in ex.shape)
+        ctx.save_for_backward(Ex, duty)
+        ctx.mark_non_differentiable(Ex)
+        return loss, Ex
+
+    @staticmethod
+    def backward(ctx, g, _g_ex):
+        Ex, duty = ctx.saved_tensors
+        b, _, h, w = ctx.shape
+        g = g.contiguous().float().reshape(1)
+        grad = torch.empty(ctx.shape, dtype=torch.float32, device=Ex.device)
+        with torch.cuda.device_of(Ex):
+            rc = N.lib().ebfi_duty_head_backward(N.ptr(g), N.ptr(Ex), N.ptr(duty), b, h, w, ctx.scale, N.ptr(grad),
+                                                 N.stream_ptr(Ex.device))
+        N.check(rc, "ebfi_duty_head_backward")
+        return grad, None, None
+
+
+class DutyMSELoss(nn.Module):
+    """Stage-1 loss of the reference (train_ours_exposuredecision.py:250-252) from the map in front of ExposureDecision's pooling:
+    forward(ex [B, 1, H, W], duty [B, 1]) -> MSELoss(sigmoid(AVGPool(ex)).view(-1, 1), duty) * scale, a 0-dim tensor; pass
+    scale = 1 / accu_step.  `Ex` holds the [B, 1] exposure estimate of the last call (detached).  Device tensors only."""
+
+    def __init__(self, scale=1.0):
+        super().__init__()
+        self.scale = float(scale)
+        self.Ex = None
+
+    def forward(self, ex, duty):
+        ex, duty = _dh_check(ex, duty)
+        if duty is None:
+            raise ValueError("DutyMSELoss needs the ground-truth duty")
+        loss, self.Ex = _DutyMSE.apply(ex, duty, self.scale)
+        return loss

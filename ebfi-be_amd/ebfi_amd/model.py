@@ -142,7 +142,9 @@ class ExposureDecision(BaseModel):
                 p.requires_grad = False
             self.eval()
 
-    def forward(self, Event, BlurryLevel):
+    def ex_map(self, Event, BlurryLevel):
+        """forward() up to Conv1: the [B, 1, H, W] map whose pooled sigmoid is the duty (the stage-1 engine puts the native
+        duty head + MSE loss of ebfi_amd.loss.DutyMSELoss on it)."""
         ev = self.EventFeatExtract(Event)
         bl = self.BLFeatExtract(BlurryLevel)
         cat = fused.ed_head(ev, bl, self.GroupNorm)    # GN x2 -> pooled product -> sigmoid -> cat([ev * atten, bl]) as one node
@@ -150,8 +152,10 @@ class ExposureDecision(BaseModel):
             # sigmoid(AVGPool(GN(ev) * GN(bl))): the pooled product as one reduction (the product map is never written)
             atten = torch.sigmoid(fused.product_mean(norm.group_norm(ev, self.GroupNorm), norm.group_norm(bl, self.GroupNorm)))
             cat = fused.scale_cat(ev, atten, bl)                # cat([ev * atten, bl], 1) as one fused stage
-        ex = self.Conv1(cat)
-        return torch.sigmoid(self.AVGPool(ex).view(-1, 1))
+        return self.Conv1(cat)
+
+    def forward(self, Event, BlurryLevel):
+        return torch.sigmoid(self.AVGPool(self.ex_map(Event, BlurryLevel)).view(-1, 1))
 
 
 class ResidualControl(BaseModel):

@@ -1,0 +1,218 @@
+#!/usr/bin/env python3
+"""train_ours_exposuredecision.py -- stage 1 of the reference's two-stage recipe on an MI355X: ExposureDecision alone is fitted
+to the ground-truth exposure duty of the data (reference train_ours_exposuredecision.py:188-326, :521-592, :703-790).
+
+Stage 2 is train_ours.py with `model.args.LoadPretrainEX: True` and `PretrainedEXPath` pointing at a checkpoint written here
+(optionally `FrozenEX: True`).  The checkpoint layout is the reference's: {model:{name:"ExposureDecision", states}, lr_scheduler,
+optimizer, config, trainer:{training_mode, iteration, monitor_best}} in checkpoint-iteration{it}.pth /
+model_best_until_iteration{it}.pth; `states` is what ExposureDecision.load_pretrain reads.
+
+The iteration body follows the reference: every period of a load is one micro-step -- blur-level map (model.BlurryFashion) ->
+ExposureDecision -> MSELoss(Ex, ExposureDuty) / accu_step -> backward -- and every accu_step-th micro-step takes the Adam step,
+logs, validates (valid_loss = the reference's sum over a load's periods of MSELoss; valid_mae beside it), saves, then steps the
+lr scheduler.  Settings, scheduler, monitor / early stop, checkpoints and resume are train_ours.py's own helpers; the engine is
+ebfi_amd.exposure_engine.ExposureEngine.  Data: synthetic batches or, with --data, recorded clips through ebfi_amd.clipdata.
+TensorBoard and image dumps of the reference are out of scope.
+
+    python train_ours_exposuredecision.py -c config/train_ours_exposuredecision.yml -id ex --iterations 200
+    python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train_ours_exposuredecision.py -id ex
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+import torch.distributed as dist
+import yaml
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+
+from train_ours import (CHECKPOINT_KEYS, TRAINING_MODE, Monitor, best_checkpoint_name, build_lr_scheduler,  # noqa: E402,F401
+                        checkpoint_state, init_distributed_mode, resume_checkpoint, run_validation, save_checkpoint,
+                        trainer_settings, validation_seeds, validation_settings)
+from ebfi_amd.dp import reduce_tensor  # noqa: E402
+from ebfi_amd.exposure_engine import (BLURRY_FASHIONS, check_fashion, check_model_name,  # noqa: E402,F401
+                                      synthetic_exposure_batch)
+
+DEFAULT_CONFIG = os.path.join(HERE, "config", "train_ours_exposuredecision.yml")
+DEFAULT_EXPOSURE_TIME = list(range(1, 16))          # ExposureTime of the reference's stage-1 config (Custom exposure)
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Stage-1 pre-training of ExposureDecision")
+    # the reference's command line (train_ours_exposuredecision.py:774-792)
+    ap.add_argument("-c", "--config", default=DEFAULT_CONFIG)
+    ap.add_argument("-id", "--runid", default=None, help="run name (default: the config's `id`, else 'run')")
+    ap.add_argument("-seed", "--seed", type=int, default=123)
+    ap.add_argument("-r", "--resume", default=None, help="checkpoint to resume from")
+    ap.add_argument("--reset", action="store_true", help="with --resume: load the model only, restart optimiser / schedule / count")
+    ap.add_argument("--limited_memory", action="store_true",
+                    help="accepted for the reference's command line (there it switches the sharing strategy of the data loader's "
+                         "worker processes; this trainer has none)")
+    ap.add_argument("-lr", "--learning_rate", type=float, default=None, help="overrides optimizer.args.lr")
+    ap.add_argument("-bs", "--batch_size", type=int, default=None, help="overrides the per-GPU batch size")
+    # what train_ours.py adds
+    ap.add_argument("--iterations", type=int, default=None)
+    ap.add_argument("--precision", default="bf16x3", choices=["fp32", "bf16x3"],
+                    help="matrix-core operands of the convs: bf16x3 = split bf16 pairs, fp32-grade accuracy (default); fp32 = exact")
+    ap.add_argument("--graph", action="store_true", help="replay forward+loss+backward from a captured hipGraph")
+    ap.add_argument("--host-data", action="store_true", help="draw every synthetic batch on the host (bit-identical across machines)")
+    ap.add_argument("--data", default=None,
+                    help="recorded clips instead of synthetic batches (a directory of .npz / .h5 clips, a datalist .txt or one clip "
+                         "file, ebfi_amd.clipdata); train_dataloader.dataset of the config sets periods / exposure / crop")
+    ap.add_argument("--valid-data", default=None,
+                    help="validation clips instead of valid_dataloader.path_to_datalist_txt (with trainer.do_validation; without "
+                         "either: a fixed set of trainer.valid_batches synthetic batches)")
+    return ap
+
+
+def exposure_settings(config):
+    """What stage 1 reads beyond trainer_settings: model.name (checked), model.BlurryFashion (checked; the reference keeps it
+    beside `args`, :113), model.args, TB = EventInch / 2, and the exposure lottery of the synthetic batches (dataset keys)."""
+    model = config["model"]
+    name = check_model_name(model["name"])
+    fashion = check_fashion(model.get("BlurryFashion", (model.get("args") or {}).get("BlurryFashion")))
+    margs = {k: v for k, v in (model.get("args") or {}).items() if k != "BlurryFashion"}
+    event_inch = int(margs.get("EventInch", 32))
+    if event_inch % 2:
+        raise ValueError("model.args.EventInch must be 2 * TIME_BINS, got %d" % event_inch)
+    ds = ((config.get("train_dataloader") or {}).get("dataset") or {})
+    tr = config.get("trainer", {}) or {}
+    return {"name": name, "fashion": fashion, "model_args": margs, "TB": event_inch // 2,
+            "exposure_time": list(ds.get("ExposureTime", DEFAULT_EXPOSURE_TIME)),
+            "frames_per_period": int(ds.get("NumFramePerPeriod", 16)),
+            "batch_size": int(tr.get("batch_size", (config.get("train_dataloader") or {}).get("batch_size", 4))),
+            "height": int(tr.get("height", 128)), "width": int(tr.get("width", 128))}
+
+
+def _clip_dataset(path, ds_cfg, es, device, seed):
+    from ebfi_amd import clipdata
+    return clipdata.ClipDataset(path, time_bins=int(ds_cfg.get("time_bins", es["TB"])),
+                                frames_per_period=int(ds_cfg.get("NumFramePerPeriod", 16)),
+                                frames_per_blurry=int(ds_cfg.get("NumFramePerBlurry", 16)),
+                                exposure_method=ds_cfg.get("ExposureMethod", "Custom"),
+                                exposure_time=ds_cfg.get("ExposureTime", DEFAULT_EXPOSURE_TIME),
+                                device=device, seed=seed, **clipdata.dataset_args_from_config(ds_cfg))
+
+
+def real_data_periods(path, config, es, device, rank, world, seed):
+    """Endless stream of (Frame [B,3,H,W], Event [B,TB,2,H,W], Duty [B,1]) micro-steps from recorded clips: one per period of
+    every load of a collated batch, in the reference's order (:221-231)."""
+    from ebfi_amd import clipdata
+    ds = _clip_dataset(path, (config.get("train_dataloader") or {}).get("dataset") or {}, es, device, seed)
+    B = es["batch_size"]
+    if len(ds) < B * world:
+        raise SystemExit("--data: %d periods in %s, need at least batch_size x world = %d" % (len(ds), path, B * world))
+    for batch in clipdata.batches(ds, B, rank=rank, world=world, seed=seed):
+        frames, events, duties = batch["SeqBlurryF"], batch["SeqHREv"], batch["SeqExposureDuty"]
+        for load in range(frames.shape[1]):
+            for i in range(frames.shape[2]):
+                yield frames[:, load, i].contiguous(), events[:, load].contiguous(), duties[:, load, i].contiguous()
+
+
+def validation_batches(vs, es, args, device, rank, world):
+    """-> a function that yields this rank's validation batches, the same ones at every stamp (as train_ours.validation_batches):
+    recorded clips as collated dicts, or `valid_batches` synthetic (Frame, Event, Duty) periods made once."""
+    from ebfi_amd import clipdata
+    vb = vs["batch_size"] or es["batch_size"]
+    if vs["valid_data"]:
+        ds = _clip_dataset(vs["valid_data"], vs["dataset"], es, device, args.seed)
+        if len(ds) == 0:
+            raise SystemExit("--valid-data: no complete period in %s" % vs["valid_data"])
+        return lambda: clipdata.eval_batches(ds, vb, rank=rank, world=world, seed=args.seed, drop_last=vs["drop_last"])
+    seeds = validation_seeds(args.seed, vs["valid_batches"])
+    mine = [synthetic_exposure_batch(vb, es["height"], es["width"], es["TB"], es["exposure_time"], es["frames_per_period"],
+                                     device=device, seed=seeds[j]) for j in clipdata.shard_indices(len(seeds), rank, world)]
+    return lambda: iter(mine)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    with open(args.config) as fh:
+        config = yaml.safe_load(fh)
+    tr = config.get("trainer", {}) or {}
+    st = trainer_settings(config, args.iterations)
+    vs = validation_settings(config, args.valid_data)
+    es = exposure_settings(config)
+    if args.batch_size:
+        es["batch_size"] = int(args.batch_size)
+    assert config["optimizer"]["name"] == "Adam", "only Adam (config/train_ours_exposuredecision.yml) is implemented"
+    rank, world, gpu = init_distributed_mode()
+    device = torch.device("cuda", gpu)
+    oargs = config["optimizer"].get("args", {}) or {}
+    from ebfi_amd.exposure_engine import ExposureEngine
+    from ebfi_amd.metrics import MetricTracker
+
+    eng = ExposureEngine(es["model_args"], fashion=es["fashion"], device=device, precision=args.precision,
+                         lr=float(args.learning_rate or oargs.get("lr", 1e-4)), betas=tuple(oargs.get("betas", (0.9, 0.999))), seed=args.seed,
+                         graph=args.graph or bool(tr.get("graph", False)), accu_step=st["accu_step"], name=es["name"])
+    scheduler = build_lr_scheduler(config, eng.optimizer.inner)
+    monitor = Monitor(vs["monitor"], vs["early_stop"],
+                      warn=None if rank == 0 else (lambda msg: None)) if vs["do_validation"] else None
+    start = resume_checkpoint(args.resume, eng, scheduler, config, reset=args.reset, map_location=device,
+                              monitor=monitor) if args.resume else 0
+    B, H, W, TB = es["batch_size"], es["height"], es["width"], es["TB"]
+    runid = args.runid or str(config.get("id") or "run")
+    out_dir = os.path.join(tr.get("output_path", "./output"), "models", config.get("experiment", "ExposurePretrain"), runid)
+
+    real = real_data_periods(args.data, config, es, device, rank, world, args.seed) if args.data else None
+    valid_stamp, valid_batches, tracker = 1, None, None
+    if vs["do_validation"]:
+        valid_batches = validation_batches(vs, es, args, device, rank, world)
+        tracker = MetricTracker(eng.VALID_KEYS)
+    t0, samples, it = None, 0, start
+    while it < st["iterations"]:
+        for micro in range(st["accu_step"]):
+            if real is not None:
+                batch = next(real)
+            else:
+                batch = synthetic_exposure_batch(B, H, W, TB, es["exposure_time"], es["frames_per_period"], device=device,
+                                                 seed=args.seed + 1000 * (it * st["accu_step"] + micro), rank=rank,
+                                                 on_device=not args.host_data)
+            loss = eng.train_step(*batch)
+            if t0 is not None:
+                samples += B * world
+        log_now = it % st["log_step"] == 0 or it == st["iterations"] - 1
+        if log_now:                      # the loss all-reduce is for logging only (:260-261)
+            loss = reduce_tensor(loss.clone())
+        lr_now = scheduler.get_last_lr()[0] if scheduler is not None else eng.optimizer.param_groups[0]["lr"]
+        if rank == 0 and log_now:
+            torch.cuda.synchronize()
+            rate = samples / (time.perf_counter() - t0) if t0 is not None and samples else float("nan")
+            print("Iteration: %d/%d train_loss: %.4e learning rate: %.4e  %.1f samples/s"
+                  % (it, st["iterations"], loss.item(), lr_now, rate), flush=True)
+        if t0 is None and eng.settled:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        best = stop = False
+        if vs["do_validation"] and it % vs["valid_step"] == 0 and it != 0:          # :287-304
+            t_valid = time.perf_counter()
+            val_log = run_validation(eng, valid_batches, tracker, valid_stamp, vs["valid_log_step"], rank)
+            if t0 is not None:
+                t0 += time.perf_counter() - t_valid
+            stop, best = monitor.evaluate(val_log)
+            if rank == 0:
+                print("Valid stamp: %d %s (best %r)" % (valid_stamp, " ".join("%s: %.6e" % (k, val_log[k]) for k in eng.VALID_KEYS),
+                                                        monitor.best), flush=True)
+                if stop:
+                    print(monitor.stop_message(), flush=True)
+            valid_stamp += 1
+        if rank == 0 and ((st["save_period"] and it % st["save_period"] == 0 and it != 0) or best or stop
+                          or it == st["iterations"] - 1):
+            path = os.path.join(out_dir, "checkpoint-iteration%d.pth" % it)
+            for p in save_checkpoint(path, eng, scheduler, config, it, monitor.best if monitor is not None else None, best):
+                print("saved", p, flush=True)
+        if stop:
+            it += 1
+            break
+        if scheduler is not None and it % st["lr_change_rate"] == 0 and it != 0 and lr_now >= st["lr_min"]:   # :311-314
+            scheduler.step()
+        it += 1
+    if world > 1:
+        dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()

@@ -39,6 +39,8 @@
  *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
  *   ebfi_lpips_*                perceptual_loss(net='alex') of the evaluation loop (loss/restore.py:10-40, LPIPS v0.1)
  *   ebfi_charbonnier_*          CharbonnierLoss of the validation loop (loss/restore.py:95-105, train_ours.py:588)
+ *   ebfi_duty_head_*            tail of ExposureDecision.forward + nn.MSELoss of stage 1 (model_singleframe.py:75-76,
+ *                               train_ours_exposuredecision.py:250-252)
  */
 #ifndef EBFI_HIP_H
 #define EBFI_HIP_H
@@ -77,7 +79,8 @@ extern "C" {
  *      existing entry point changed, so a caller built against an earlier 14 header still calls every function it knows with
  *      the right arguments, and the binding's version check has nothing new to refuse; later still, as another pure addition
  *      under 14, ebfi_lpips_params_bytes / _pack_params / _workspace / _alex (evaluation LPIPS, AlexNet v0.1); and, again as a
- *      pure addition under 14, ebfi_charbonnier_workspace / _forward / _backward (the validation loop's Charbonnier loss) */
+ *      pure addition under 14, ebfi_charbonnier_workspace / _forward / _backward (the validation loop's Charbonnier loss); and
+ *      ebfi_duty_head_workspace / _forward / _backward (the duty head and MSE loss of the stage-1 pre-training), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -683,6 +686,31 @@ int ebfi_charbonnier_forward(const float *x, const int64_t x_strides[4], const f
                              int C, int H, int W, float eps, void *workspace, int64_t workspace_bytes, float *out, void *stream);
 int ebfi_charbonnier_backward(const float *x, const int64_t x_strides[4], const float *y, const int64_t y_strides[4], int64_t N,
                               int C, int H, int W, float eps, const float *g, float *grad_x, void *stream);
+
+/* ------------------------------------------------------------------ duty head + MSE loss (stage-1 pre-training)
+ * The tail of ExposureDecision.forward (reference models/Ours/model_singleframe.py:75-76) and the loss of
+ * train_ours_exposuredecision.py:250-252 for an fp32 map ex [B, 1, H, W]:
+ *   Ex[b] = sigmoid(mean over h, w of ex[b, 0, h, w])
+ *   loss  = scale * mean over b of (Ex[b] - duty[b])^2        -- MSELoss(Ex, duty) / accu_step with scale = 1 / accu_step
+ * The plane sum is accumulated in fp64 from the fp32 elements, mean and sigmoid are formed in fp64 and Ex[b] is rounded to
+ * fp32 once; the loss is summed in fp64 over the ROUNDED Ex (what backward reads) and rounded once.  A NaN or inf element
+ * reaches its own sample's Ex and the loss, no other sample's Ex: nothing is masked.  duty == NULL: Ex only (loss_out unused).
+ * ex_strides (elements, any int64) of B, the single channel (ignored) and rows; the column stride must be 1
+ * (EBFI_ERR_UNSUPPORTED otherwise).  16-byte loads when the base pointer is 16-byte aligned and both strides are multiples
+ * of 4, scalar loads otherwise and for a ragged row tail.
+ * Forward: two launches on `stream` (one fp64 partial per tile of R = ceil(4096 / W) rows into `workspace`, then ONE workgroup
+ * that reduces in a fixed order): no host synchronisation, no allocation, no atomics -- capturable, and bit-reproducible.
+ * workspace: 16-byte aligned, at least ebfi_duty_head_workspace(B, H, W) = B * ceil(H / R) * 8 bytes (pure host arithmetic; 0
+ * for a bad shape).  duty: device float[B]; Ex_out: device float[B]; loss_out: device float[1].
+ * Backward: grad_ex[b, :, :] = g[0] * scale * 2 (Ex[b] - duty[b]) / B * Ex[b] (1 - Ex[b]) / (H * W), g a device scalar, one
+ * streaming fill of a CONTIGUOUS [B, 1, H, W] tensor; a plane is constant bit for bit.
+ * Null pointers (other than duty in forward), B < 0, H / W < 1, a non-finite scale, a misaligned workspace -> EBFI_ERR_ARG;
+ * a short workspace -> EBFI_ERR_WORKSPACE; none of them touches the GPU. */
+int64_t ebfi_duty_head_workspace(int64_t B, int H, int W);
+int ebfi_duty_head_forward(const float *ex, const int64_t ex_strides[4], const float *duty, int64_t B, int H, int W, float scale,
+                           void *workspace, int64_t workspace_bytes, float *Ex_out, float *loss_out, void *stream);
+int ebfi_duty_head_backward(const float *g, const float *Ex, const float *duty, int64_t B, int H, int W, float scale,
+                            float *grad_ex, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the

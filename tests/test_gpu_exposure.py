@@ -1,0 +1,373 @@
+"""GPU checks of the stage-1 (ExposureDecision pre-training) path: the duty-head kernels against the float64 restatement of
+tests/test_exposure_host.py, the blur-level inputs and one ExposureEngine step against the CPU oracle, graph replay and gradient
+accumulation, the loss sequence against a CPU Adam restatement, validation, and the entry point with its hand-over to stage 2."""
+import functools
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+import yaml
+
+pytestmark = pytest.mark.gpu
+
+from oracle import model_ref  # noqa: E402
+from test_exposure_host import CONFIG, ROOT, ref_duty_head, ref_duty_head_grad  # noqa: E402
+
+LOSS_TOL, GRAD_TOL, PER_PARAM_TOL = 1e-3, 5e-3, 5e-2      # the bars of test_gpu_model.py::test_benchmarked_step_vs_oracle
+CASES = ["1x1", "5x7x9", "2x64x64", "3x37x129", "strided", "offset4", "2x720x1280"]
+
+
+# ------------------------------------------------------------------------------------------------ duty-head kernels
+def _fill(shape, seed):
+    """ex uniform in [-4, 4] plus a per-sample offset: the plane means span roughly [-3, 3]."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    B = shape[0]
+    off = torch.linspace(-3.0, 3.0, B) if B > 1 else torch.tensor([1.0])
+    return torch.rand(shape, generator=g) * 8.0 - 4.0 + off.view(B, 1, 1, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    """-> (ex device tensor (possibly a strided / offset view), ex as float64 numpy, duty [B, 1] device, duty numpy).  Shared by the
+    tests below, never written to."""
+    if name == "strided":            # rows of 128 cut from rows of 160: row stride 160, 16-byte aligned start
+        base = _fill((2, 1, 40, 160), 21).cuda()
+        ex = base[:, :, 3:35, 8:136]
+        assert not ex.is_contiguous() and ex.data_ptr() % 16 == 0 and ex.stride(3) == 1
+    elif name == "offset4":          # the base pointer 4 bytes past a 16-byte boundary
+        vals = _fill((2, 1, 16, 24), 22)
+        flat = torch.empty(vals.numel() + 1, device="cuda")
+        flat[1:].copy_(vals.reshape(-1))
+        ex = flat[1:].view(2, 1, 16, 24)
+        assert ex.data_ptr() % 16 == 4
+    else:
+        dims = [int(v) for v in name.split("x")]
+        shape = (dims[0], 1, dims[1], dims[2]) if len(dims) == 3 else (1, 1, 1, 1)
+        ex = _fill(shape, 20 + len(name)).cuda()
+    ex64 = ex.cpu().double().numpy()
+    Ex64, _ = ref_duty_head(ex64)
+    duty = np.empty(len(Ex64))
+    for b, e in enumerate(Ex64):     # a multiple of 1/16 at least 0.05 away from the exact estimate
+        ks = [(5 * b + 3 + j) % 17 for j in range(17)]
+        duty[b] = next(k for k in ks if abs(e - k / 16.0) >= 0.05) / 16.0
+    assert (np.abs(Ex64 - duty) >= 0.05).all()
+    return ex, ex64, torch.tensor(duty, dtype=torch.float32).view(-1, 1).cuda(), duty
+
+
+def _run(ex, duty, scale=0.5, g=2.5):
+    from ebfi_amd.loss import DutyMSELoss
+    x = ex.detach().requires_grad_(True)         # (keeps the view's strides and storage offset)
+    crit = DutyMSELoss(scale)
+    loss = crit(x, duty)
+    (loss * g).backward()
+    return loss.detach(), crit.Ex, x.grad
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_duty_head_forward_vs_float64(name):
+    """Ex within 1e-6 absolute (the plane mean is an fp64 sum of exact fp32 values, rounded once after the sigmoid: 6e-8, the rest
+    is margin), the loss within 1e-5 relative (2 * 1e-6 / 0.05 = 4e-5 would be the worst case of an Ex at its bound; an Ex rounded
+    once gives 2.4e-6); the loss-free form returns the same Ex bit for bit."""
+    from ebfi_amd.loss import duty_head
+    ex, ex64, duty, duty64 = _case(name)
+    loss, Ex, _ = _run(ex, duty)
+    Ex64, loss64 = ref_duty_head(ex64, duty64, 0.5)
+    assert Ex.shape == (ex.shape[0], 1) and loss.dim() == 0 and Ex.dtype == loss.dtype == torch.float32
+    err = np.abs(Ex.cpu().double().numpy().ravel() - Ex64).max()
+    rel = abs(loss.item() - loss64) / loss64
+    print("duty head %-11s |Ex - Ex64| %.3e  loss rel %.3e  means %s" % (name, err, rel, np.round(np.log(Ex64 / (1 - Ex64)), 2)))
+    assert err <= 1e-6, err
+    assert rel <= 1e-5, rel
+    assert torch.equal(duty_head(ex), Ex)
+
+
+def test_duty_head_propagates_nan_to_its_sample_only():
+    from ebfi_amd.loss import duty_head
+    ex, _, duty, _ = _case("3x37x129")
+    clean = duty_head(ex)
+    for pos in ((1, 0, 0, 0), (1, 0, 5, 128)):       # first element of a plane; last element of a ragged row (W = 129)
+        bad = ex.clone()
+        bad[pos] = float("nan")
+        loss, Ex, _ = _run(bad, duty)
+        assert torch.isnan(Ex[1]).all() and torch.isnan(loss), pos
+        assert torch.equal(Ex[[0, 2]], clean[[0, 2]]), pos
+        assert torch.equal(duty_head(bad)[[0, 2]], clean[[0, 2]]) and torch.isnan(duty_head(bad)[1]).all()
+    inf = ex.clone()
+    inf[2, 0, 36, 128] = float("inf")
+    assert duty_head(inf)[2].item() == 1.0 and torch.equal(duty_head(inf)[:2], clean[:2])
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_duty_head_backward_vs_float64(name):
+    """Upstream gradient 2.5, scale 0.5: 1e-4 relative per element (the 1e-6 of Ex against |Ex - duty| >= 0.05 gives 2e-5, the rest
+    is margin); constant over each plane bit for bit; the forward / backward pair twice gives identical bits."""
+    ex, ex64, duty, duty64 = _case(name)
+    loss, Ex, grad = _run(ex, duty, 0.5, 2.5)
+    ref = ref_duty_head_grad(ex64, duty64, 0.5, 2.5)
+    got = grad.cpu().double().numpy()
+    assert got.shape == ref.shape
+    rel = np.abs(got - ref) / np.abs(ref)
+    print("duty head bwd %-11s worst rel %.3e" % (name, rel.max()))
+    assert rel.max() <= 1e-4, rel.max()
+    assert torch.equal(grad, grad[:, :, :1, :1].expand_as(grad))
+    loss2, Ex2, grad2 = _run(ex, duty, 0.5, 2.5)
+    assert torch.equal(loss, loss2) and torch.equal(Ex, Ex2) and torch.equal(grad, grad2)
+
+
+# ------------------------------------------------------------------------------------------------ blur-level inputs
+@pytest.mark.parametrize("fashion,channels", [("DarkCh", 1), ("Lap", 1), ("RGB", 3), ("RGBDark", 4), ("RGBLap", 4)])
+def test_blurry_level_vs_oracle(fashion, channels):
+    """Bit-exact against the oracle's restatement: the rule tests/test_gpu_events_blur.py applies to Frame2Lap / Frame2DCP."""
+    from ebfi_amd.exposure_engine import blurry_level
+    torch.manual_seed(4)
+    f = torch.rand(2, 3, 24, 40)
+    f[0, :, 0, 0] = 1.0
+    f[0, :, -1, -1] = 0.0
+    out = blurry_level(f.cuda(), fashion)
+    assert out.shape == (2, channels, 24, 40) and out.dtype == torch.float32
+    assert np.array_equal(out.cpu().numpy(), model_ref.blurry_level(f, fashion).numpy())
+
+
+# ------------------------------------------------------------------------------------------------ engine
+BLINCH = {"DarkCh": 1, "Lap": 1, "RGB": 3, "RGBDark": 4, "RGBLap": 4}
+
+
+MULTI_STEP_FASHION = "RGBDark"
+
+
+def _engine(fashion="RGBLap", precision="fp32", weight_seed=80, **kw):
+    """An ExposureEngine with O(1)-gain weights drawn as tests/test_gpu_model.py:96 does (the x0.1 initialisation gives the
+    constant 0.5).  Parameters are views of the optimiser's flat buffer: copied in place.
+    weight_seed: at O(1) gain the unnormalised Laplacian channel of RGBLap (grey-level differences of up to several hundred)
+    puts the pooled logit at tens for most draws -- seed 11 gives Ex = 1e-25 in the float64 oracle, a step without signal.  Seed
+    80 is one whose ORACLE logits stay within [-2, 2.4] on the batches used here (checked on the oracle side in every test).
+    Even then ONE Adam step moves the RGBLap logit into saturation (oracle Ex = 0 from the second step on, at lr 1e-4 as well),
+    so the tests that take several steps use MULTI_STEP_FASHION: the same layer shapes (BLInch = 4) on inputs in [0, 1], whose
+    oracle sequence keeps Ex in 0.19 .. 0.77 and agrees between float32 and float64 to 5e-7 in the loss."""
+    from ebfi_amd.exposure_engine import ExposureEngine
+    eng = ExposureEngine(dict(EventInch=32, BLInch=BLINCH[fashion]), fashion=fashion, device="cuda", precision=precision, seed=4, **kw)
+    gen = torch.Generator(device="cpu").manual_seed(weight_seed)
+    with torch.no_grad():
+        for p in eng.model.parameters():
+            if p.dim() > 1:
+                p.copy_((torch.randn(p.shape, generator=gen) * (1.2 / p[0].numel() ** 0.5)).cuda())
+            else:
+                p.add_((0.05 * torch.randn(p.shape, generator=gen)).cuda())
+    return eng
+
+
+def _batch(B, H, W, seed):
+    from ebfi_amd.exposure_engine import synthetic_exposure_batch
+    return synthetic_exposure_batch(B, H, W, TB=16, device="cpu", seed=seed)
+
+
+def _oracle(sd, names, batch, fashion, scale=1.0):
+    """Oracle forward + MSE under CPU autograd -> (loss, Ex, packed gradient, sizes)."""
+    frame, event, duty = batch
+    sdo = {"ED." + k: v.detach().cpu().clone().requires_grad_(k in names) for k, v in sd.items()}
+    ev = event.reshape(event.size(0), -1, event.size(3), event.size(4))
+    Ex = model_ref.exposure_decision(sdo, "ED", ev, model_ref.blurry_level(frame, fashion))
+    loss = F.mse_loss(Ex, duty) * scale
+    loss.backward()
+    return loss.item(), Ex.detach(), torch.cat([sdo["ED." + n].grad.reshape(-1) for n in names]), {n: sdo["ED." + n].numel() for n in names}
+
+
+def _check_gradient(flat, ref_flat, sizes, names):
+    err = ((flat - ref_flat).norm() / ref_flat.norm()).item()
+    off, worst = 0, (0.0, None)
+    for n in names:
+        k = sizes[n]
+        g, r = flat[off:off + k], ref_flat[off:off + k]
+        off += k
+        if r.norm() > 1e-6 * ref_flat.norm():          # (gradients that vanish against the rest: pure rounding)
+            worst = max(worst, (((g - r).norm() / r.norm()).item(), n))
+    print("   packed gradient rel %.3e, worst parameter %.3e (%s)" % (err, worst[0], worst[1]))
+    assert off == flat.numel() == ref_flat.numel()
+    assert err < GRAD_TOL, err
+    assert worst[0] < PER_PARAM_TOL, worst
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+@pytest.mark.parametrize("fashion,B,H,W", [("RGBLap", 2, 32, 32), ("DarkCh", 3, 32, 40)])
+def test_one_step_vs_oracle(precision, fashion, B, H, W):
+    """Loss, Ex and every parameter gradient of one ExposureEngine step against oracle.model_ref.exposure_decision + MSE under CPU
+    autograd; DarkCh covers the thin 1 -> 64 layer."""
+    eng = _engine(fashion, precision, lr=1e-4)
+    names = [n for n, p in eng.model.named_parameters() if p.requires_grad]
+    sd = {k: v.detach().cpu().clone() for k, v in eng.model.state_dict().items()}
+    batch = _batch(B, H, W, seed=31)
+    ref_loss, ref_Ex, ref_flat, sizes = _oracle(sd, names, batch, fashion)
+    assert 0.02 < ref_Ex.min() and ref_Ex.max() < 0.98 and ref_loss > 1e-4        # (the step carries signal: no saturated sigmoid)
+    loss = eng.train_step(*[v.cuda() for v in batch])
+    flat = eng.bucket.flat.detach().cpu().clone()
+    print("one step %s %s: loss %.6e (oracle %.6e), Ex %s" % (precision, fashion, loss.item(), ref_loss, eng.last_Ex.flatten().tolist()))
+    assert abs(loss.item() - ref_loss) <= LOSS_TOL * abs(ref_loss), (loss.item(), ref_loss)
+    assert ((eng.last_Ex.cpu() - ref_Ex).abs().max() / ref_Ex.abs().max()).item() < LOSS_TOL
+    _check_gradient(flat, ref_flat, sizes, names)
+    assert eng.iteration == 1 and eng.bucket.views_intact()
+    moved = sum((eng.model.state_dict()[k].cpu() - sd[k]).abs().sum().item() for k in sd)
+    assert moved > 0
+
+
+def test_graph_replay_is_bit_identical_to_eager():
+    batches = [[v.cuda() for v in _batch(2, 32, 32, seed=40 + k)] for k in range(2)]
+    order = [0, 1, 0]
+    out = {}
+    for graph in (False, True):
+        eng = _engine(MULTI_STEP_FASHION, "bf16x3", lr=1e-3, graph=graph)
+        losses = [eng.train_step(*batches[k]).clone() for k in order]
+        torch.cuda.synchronize()
+        assert eng.iteration == 3
+        if graph:
+            assert eng.use_graph and not eng.graph_capture_failed and len(eng._graphs) == 1
+        out[graph] = (torch.stack(losses), eng.optimizer.flat.detach().clone())
+    assert torch.equal(out[False][0], out[True][0]), (out[False][0], out[True][0])
+    assert torch.equal(out[False][1], out[True][1])
+    assert len(set(out[True][0].tolist())) == 3
+
+
+def test_accumulation_takes_one_step_on_the_summed_gradient():
+    a, b = ([v.cuda() for v in _batch(2, 32, 32, seed=50 + k)] for k in range(2))
+    eng = _engine(MULTI_STEP_FASHION, "fp32", lr=1e-3, accu_step=2)
+    before = eng.optimizer.flat.detach().clone()
+    micro = []
+    for batch in (a, b):            # the two half-weighted micro-step gradients, eagerly, at the unchanged weights
+        eng.bucket.zero()
+        eng._fwd_bwd(*batch)
+        micro.append(eng.bucket.gather().clone())
+    assert eng.iteration == 0 and torch.equal(eng.optimizer.flat.detach(), before)
+    la = eng.train_step(*a)
+    assert eng.iteration == 0 and torch.equal(eng.optimizer.flat.detach(), before)      # first micro-step: no update
+    lb = eng.train_step(*b)
+    assert eng.iteration == 1 and not torch.equal(eng.optimizer.flat.detach(), before)
+    assert torch.equal(eng.bucket.flat, micro[0] + micro[1])
+    assert float(eng.optimizer.inner.state[eng.optimizer.flat]["step"]) == 1.0
+    # half-weighted: each loss is MSE / 2
+    full = _engine(MULTI_STEP_FASHION, "fp32", lr=1e-3)
+    full.bucket.zero()
+    la_full, _ = full._fwd_bwd(*a)
+    assert abs(la.item() - 0.5 * la_full.item()) <= 1e-6 * la_full.item() and lb.item() > 0
+
+
+def test_loss_sequence_vs_cpu_adam():
+    """Three optimiser steps against the CPU restatement -- oracle forward, torch autograd, torch.optim.Adam at the same lr and
+    betas: the loss within the 1e-3 bar at every step."""
+    lr, betas = 1e-3, (0.9, 0.999)
+    eng = _engine(MULTI_STEP_FASHION, "bf16x3", lr=lr, betas=betas)
+    names = [n for n, p in eng.model.named_parameters() if p.requires_grad]
+    params = {"ED." + k: v.detach().cpu().clone().requires_grad_(k in names) for k, v in eng.model.state_dict().items()}
+    opt = torch.optim.Adam([params["ED." + n] for n in names], lr=lr, betas=betas)
+    for k in range(3):
+        frame, event, duty = batch = _batch(2, 32, 32, seed=60 + k)
+        opt.zero_grad()
+        ev = event.reshape(2, -1, 32, 32)
+        Ex = model_ref.exposure_decision(params, "ED", ev, model_ref.blurry_level(frame, MULTI_STEP_FASHION))
+        ref = F.mse_loss(Ex, duty)
+        assert 0.05 < Ex.min() and Ex.max() < 0.95            # (the sequence keeps its signal: no saturated sigmoid)
+        ref.backward()
+        opt.step()
+        loss = eng.train_step(*[v.cuda() for v in batch])
+        print("step %d: loss %.6e, CPU restatement %.6e" % (k, loss.item(), ref.item()))
+        assert abs(loss.item() - ref.item()) <= LOSS_TOL * abs(ref.item()), (k, loss.item(), ref.item())
+
+
+def test_validate_matches_the_reference_sum_and_leaves_the_state():
+    from ebfi_amd import conv
+    twin = {}
+    g = torch.Generator(device="cpu").manual_seed(70)
+    frames = torch.rand(2, 2, 3, 32, 32, generator=g).cuda()                       # [B, NumP = 2, 3, H, W]
+    event = torch.poisson(torch.full((2, 16, 2, 32, 32), 0.35), generator=g).cuda()
+    duties = torch.tensor([[[0.5625], [0.75]], [[0.9375], [0.25]]]).cuda()          # [B, NumP, 1]
+    step = [v.cuda() for v in _batch(2, 32, 32, seed=71)]
+    for validate in (False, True):
+        eng = _engine(MULTI_STEP_FASHION, "bf16x3", lr=1e-3, graph=True)
+        l1 = eng.train_step(*step)
+        if validate:
+            eng.model.GroupNorm.eval()                       # (a sub-module held in eval must stay so)
+            params = eng.optimizer.flat.detach().clone()
+            grads = [(p.grad, p.grad.clone()) for p in eng.bucket.params]
+            graphs = dict(eng._graphs)
+            vals = eng.validate((frames, event, duties))
+            assert set(vals) == {"valid_loss", "valid_mae"} == set(eng.VALID_KEYS)
+            assert all(v.dim() == 0 and v.is_cuda and v.dtype == torch.float64 for v in vals.values())
+            # the reference's _valid: model.eval(); loss = sum over the periods of MSELoss(Ex, ExposureDuty)
+            want, mae, slack = 0.0, 0.0, 0.0
+            for i in range(2):
+                Ex = eng.predict(frames[:, i], event)
+                want += F.mse_loss(Ex, duties[:, i]).item()
+                d = (Ex - duties[:, i]).abs().double()
+                mae += d.mean().item() / 2
+                slack += (2 * d * 2e-6).mean().item()        # Ex of the native head (<= 1e-6 off) against the fp32 torch tail (likewise)
+            assert abs(vals["valid_loss"].item() - want) <= slack + 1e-6 * want, (vals["valid_loss"].item(), want, slack)
+            assert abs(vals["valid_mae"].item() - mae) <= 2e-6 + 1e-6 * mae
+            assert torch.equal(eng.optimizer.flat.detach(), params)
+            assert all(p.grad is g0 and torch.equal(g0, g1) for p, (g0, g1) in zip(eng.bucket.params, grads))
+            assert eng.model.training and not eng.model.GroupNorm.training and eng.model.Conv1.training
+            assert list(eng._graphs) == list(graphs) and all(eng._graphs[k] is graphs[k] for k in graphs) and eng.iteration == 1 and eng._micro == 0 and conv.get_compute_dtype() == "fp32"
+            eng.model.GroupNorm.train()
+        l2 = eng.train_step(*step)
+        twin[validate] = (l1.clone(), l2.clone(), eng.optimizer.flat.detach().clone())
+    assert all(torch.equal(x, y) for x, y in zip(twin[False], twin[True]))       # the captured graph replays as if nothing happened
+
+
+# ------------------------------------------------------------------------------------------------ entry point
+def _child(args, cwd):
+    env = dict(os.environ, EBFI_STRICT_NATIVE="1")
+    env.pop("EBFI_DEV", None)
+    script = os.path.join(ROOT, "ebfi-be_amd", "train_ours_exposuredecision.py")
+    res = subprocess.run(["timeout", "-k", "10", "240", sys.executable, script] + args, cwd=cwd, env=env, capture_output=True, text=True)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    return res.stdout
+
+
+def test_entry_point_writes_checkpoints_resumes_and_feeds_stage2(tmp_path):
+    from ebfi_amd.engine import DEFAULT_MODEL_ARGS
+    from ebfi_amd.exposure_engine import ExposureEngine, blurry_level
+    from ebfi_amd.model import EVFIAutoEx
+    cfg = yaml.safe_load(open(CONFIG))
+    cfg["trainer"].update(output_path=str(tmp_path / "out"), do_validation=True, batch_size=2, height=32, width=32, valid_batches=1)
+    cfg["trainer"]["iteration_based_train"].update(iterations=6, save_period=3, valid_step=2, train_log_step=1)
+    cfg_path = str(tmp_path / "stage1.yml")
+    yaml.safe_dump(cfg, open(cfg_path, "w"))
+    out = _child(["-c", cfg_path, "-id", "t", "-seed", "5", "--precision", "fp32", "--host-data"], str(tmp_path))
+    run = tmp_path / "out" / "models" / "ExposurePretrain" / "t"
+    files = sorted(os.listdir(run))
+    # save_period 3 -> 3; validation at 2 and 4 (the first stamp is always a best one) -> 2 (+ best); the last iteration -> 5
+    assert {"checkpoint-iteration2.pth", "model_best_until_iteration2.pth", "checkpoint-iteration3.pth",
+            "checkpoint-iteration5.pth"} <= set(files), files
+    assert all(f.startswith(("checkpoint-iteration", "model_best_until_iteration")) for f in files)
+    assert "Valid stamp: 1" in out and "Valid stamp: 2" in out and "Iteration: 5/6" in out
+    cpts = {f: torch.load(str(run / f), map_location="cpu", weights_only=False) for f in files}
+    for f, c in cpts.items():
+        assert tuple(c) == ("model", "lr_scheduler", "optimizer", "config", "trainer"), f
+        assert c["model"]["name"] == "ExposureDecision" and c["trainer"]["training_mode"] == "iteration_based_train"
+    last = cpts["checkpoint-iteration5.pth"]
+    assert last["trainer"]["iteration"] == 5 and last["trainer"]["monitor_best"] is not None
+    # --resume continues at iteration + 1 and carries monitor_best
+    out2 = _child(["-c", cfg_path, "-id", "t2", "-seed", "5", "--precision", "fp32", "--host-data", "--iterations", "8",
+                   "-r", str(run / "checkpoint-iteration5.pth")], str(tmp_path))
+    assert "Iteration: 6/8" in out2 and "Iteration: 7/8" in out2 and "Iteration: 5/8" not in out2
+    run2 = tmp_path / "out" / "models" / "ExposurePretrain" / "t2"
+    c7 = torch.load(str(run2 / "checkpoint-iteration7.pth"), map_location="cpu", weights_only=False)
+    assert c7["trainer"]["iteration"] == 7
+    if (run2 / "model_best_until_iteration6.pth").exists():
+        assert c7["trainer"]["monitor_best"] <= last["trainer"]["monitor_best"]
+    else:
+        assert c7["trainer"]["monitor_best"] == last["trainer"]["monitor_best"]
+    # stage 2 loads what stage 1 wrote: the same Ex from both models, bit for bit, in fp32 mode
+    best = sorted(f for f in files if f.startswith("model_best_until_iteration"))[-1]
+    net = EVFIAutoEx(**dict(DEFAULT_MODEL_ARGS, LoadPretrainEX=True, PretrainedEXPath=str(run / best), FrozenEX=True)).cuda()
+    assert not any(p.requires_grad for p in net.ExposureDecision.parameters())
+    eng = ExposureEngine(cfg["model"]["args"], fashion=cfg["model"]["BlurryFashion"], device="cuda", precision="fp32")
+    eng.model.load_state_dict(cpts[best]["model"]["states"])
+    frame, event, _ = [v.cuda() for v in _batch(2, 32, 32, seed=80)]
+    ev = event.reshape(2, -1, 32, 32)
+    with torch.no_grad():
+        ex2 = net.ExposureDecision(ev, blurry_level(frame, "RGBLap"))
+    ex1 = eng.predict(frame, event)
+    assert ex1.shape == (2, 1) and torch.equal(ex1, ex2)
+    assert ((ex1 - 0.5).abs() > 0).any()
