@@ -25,9 +25,18 @@ Storage.  A clip is either an `.npz` file with
     ts          float64 [E]          seconds, sorted
     ps          int8 / any [E]       polarity +-1
 
+and, for an exposure-stamped recording of a real camera (RealBlurClipDataset below), two more arrays
+
+    exposure_begin_t, exposure_end_t   any numeric type [N]   when frame i's shutter opened / closed (the image attributes
+                                                              of the same names in the RealBlur-DAVIS files)
+
 or, when `h5py` is importable (it is not part of the MI355X image: the import is optional and a missing module raises a
 clear error only when an .h5 file is actually opened), an HDF5 file in the reference's own layout
 (`ori_images/image%09d` + attrs `ori_event_idx`, `ori_events/{xs,ys,ts,ps}`), read at scale 1 ('ori').
+
+Recordings of a real camera (`infer_ours.py --real_blur`) go through RealBlurClipDataset, the counterpart of the reference's
+second dataset class (dataloader/h5dataset_realdata.py): every stored frame IS a blurry input with its own exposure stamps,
+there is no sharp ground truth, and the frame reaches the device as uint8 (ebfi_amd.frameio).
 """
 import os
 import random
@@ -129,9 +138,22 @@ class _NpzClip:
             raise ValueError("%s: images must be [N,H,W,3] with one event_idx per image" % path)
         self.num_imgs = int(self.images.shape[0])
         self.resolution = (int(self.images.shape[1]), int(self.images.shape[2]))
+        self.path = path
+        self.exposure_begin_t, self.exposure_end_t = (np.asarray(z[k]) if k in z.files else None
+                                                      for k in ("exposure_begin_t", "exposure_end_t"))
+        for k, v in (("exposure_begin_t", self.exposure_begin_t), ("exposure_end_t", self.exposure_end_t)):
+            if v is not None and v.shape != (self.num_imgs,):
+                raise ValueError("%s: %s must hold one stamp per image, got shape %r" % (path, k, v.shape))
 
     def frame_bgr(self, i):
         return self.images[i]
+
+    def has_exposure(self):
+        return self.exposure_begin_t is not None and self.exposure_end_t is not None
+
+    def exposure(self, i):
+        """(exposure_begin_t, exposure_end_t) of frame i, in the stored type."""
+        return self.exposure_begin_t[i], self.exposure_end_t[i]
 
     def events(self, i0, i1):
         a, b = int(self.event_idx[i0]), int(self.event_idx[i1])
@@ -150,6 +172,7 @@ class _H5Clip:
         self.f = h5py.File(path, "r")
         self.num_imgs = len(self.f["ori_images"].keys())
         self.resolution = tuple(int(v) for v in self.f.attrs["sensor_resolution"].tolist())
+        self.path = path
 
     def frame_bgr(self, i):
         return self.f["ori_images"]["image%09d" % i][:]
@@ -159,6 +182,14 @@ class _H5Clip:
         b = self.f["ori_images"]["image%09d" % i1].attrs["ori_event_idx"]
         g = self.f["ori_events"]
         return g["xs"][a:b], g["ys"][a:b], g["ts"][a:b], g["ps"][a:b]
+
+    def has_exposure(self):
+        attrs = self.f["ori_images"]["image%09d" % 0].attrs if self.num_imgs else {}
+        return "exposure_begin_t" in attrs and "exposure_end_t" in attrs
+
+    def exposure(self, i):
+        attrs = self.f["ori_images"]["image%09d" % i].attrs          # (h5dataset_realdata.py:215-217)
+        return attrs["exposure_begin_t"], attrs["exposure_end_t"]
 
 
 def open_clip(path):
@@ -266,6 +297,88 @@ class ClipDataset:
         return self.assemble(sharp, blur, stack, duty)
 
 
+class RealBlurClipDataset:
+    """An exposure-stamped recording of a real camera, as the reference's second dataset class reads it
+    (dataloader/h5dataset_realdata.py; `infer_ours.py --real_blur`).  A PERIOD is one recorded frame: frame i is the blurry
+    input, the events between frame i and frame i + 1 are its event stream, and
+    `ExposureDuty = (end_t[i] - begin_t[i]) / (begin_t[i + 1] - begin_t[i])` comes from the stamps (GetTimestamp, :211-223);
+    the last frame only closes the last shutter period, so `num_periods = N - 1` (:113).  There is no sharp ground truth.
+
+    One ITEM is one sequence of `sequence_items` -- L loads of one period each -- in the reference's keys and shapes
+    (:169-176; no SeqLatentF):
+        SeqBlurryF [L, 1, 3, H, W]   SeqHREv [L, TB, 2, H, W]   RelativeLatentTs [L, 1, interp_num]   SeqExposureDuty [L, 1, 1]
+    The frame is the stored array WITHOUT channel reversal (GetFrames, :178-189, does not swap, unlike the synthetic-blur
+    reader).  It goes to the device as uint8 and becomes planar float there (ebfi_amd.frameio.frames_to_planar), the centre
+    crop's window handed to the kernel; the event stack is binned on the device and cropped as in ClipDataset.  Event noise is
+    drawn once per item over the whole [L, TB, 2, H, W] stack with the item's seed + 3, as AugmentData does there."""
+
+    def __init__(self, path, time_bins=16, interp_num=16, periods_per_seq=2, sliding_window_seq=2, periods_per_load=1,
+                 sliding_window_load=1, crop=None, noise=None, device="cuda"):
+        """crop: the CenterCrop size or None; noise: None or (noise_std, noise_fraction) of data_augment.noise."""
+        self.clip = open_clip(path) if isinstance(path, str) else path
+        if not self.clip.has_exposure():
+            raise ValueError("%s: a real-blur clip needs the per-frame stamps exposure_begin_t / exposure_end_t (arrays of the "
+                             ".npz layout, image attributes of the HDF5 one); this clip has none" % self.clip.path)
+        if int(periods_per_load) != 1:
+            raise ValueError("RealBlurClipDataset: one period per load (the model takes one frame), got %r" % (periods_per_load,))
+        self.time_bins, self.interp_num = int(time_bins), int(interp_num)
+        self.crop = crop
+        self.noise = None if noise is None else (float(noise[0]), float(noise[1]))
+        self.device = torch.device(device)
+        self.num_periods = self.clip.num_imgs - 1          # (the last frame only closes the last shutter period)
+        self.items = sequence_items(self.num_periods, periods_per_seq, sliding_window_seq, periods_per_load, sliding_window_load)
+
+    def __len__(self):
+        return len(self.items)
+
+    def event_list(self, left, right):
+        """The load's normalised event list (host arrays): everything from frame `left` up to frame `right + 1`
+        (GetEvents, :202-206: '+1 for get all events')."""
+        return normalise_events(*self.clip.events(left, right + 1))
+
+    def exposure_duty(self, i):
+        """Exposure period over shutter period of frame i (GetTimestamp): the differences in the stored type, the quotient in
+        float64 -- the reference's numpy scalars -- rounded to float32 once, by the caller."""
+        begin, end = self.clip.exposure(i)
+        return float(np.float64(end - begin) / np.float64(self.clip.exposure(i + 1)[0] - begin))
+
+    def timestamps(self):
+        return torch.linspace(0, 1, self.interp_num)       # on the HOST, like load_metadata (:112)
+
+    def window(self):
+        """(i, j, h, w) of the centre crop, or None when there is none (or it is not smaller than the frame)."""
+        return None if self.crop is None else crop_window(*self.clip.resolution, self.crop, "center", 1)
+
+    def host_item(self, index):
+        """Everything of an item that is host work: (frames uint8 [L, H, W, 3] as stored, the normalised event list of every
+        load, SeqExposureDuty float32 [L, 1, 1], RelativeLatentTs float32 [L, 1, interp_num])."""
+        loads = self.items[index]
+        frames = np.ascontiguousarray(np.stack([self.clip.frame_bgr(left) for left, _ in loads]))     # (no channel swap)
+        duty = torch.tensor([[[self.exposure_duty(left)]] for left, _ in loads], dtype=torch.float64).float()
+        return frames, [self.event_list(*ld) for ld in loads], duty, self.timestamps()[None, None].repeat(len(loads), 1, 1)
+
+    def __getitem__(self, index, seed=None):
+        from .encodings import events_to_stack
+        from .frameio import frames_to_planar
+        if seed is None:
+            seed = random.randint(0, 2 ** 32)
+        dev, res = self.device, self.clip.resolution
+        frames, events, duty, rel_ts = self.host_item(index)
+        win = self.window()
+        blur = frames_to_planar(torch.from_numpy(frames).to(dev), window=win)                # [L,3,h,w]
+        to = lambda a, dt: torch.from_numpy(a).to(dev, dt)
+        stack = torch.stack([events_to_stack(to(xs, torch.float64), to(ys, torch.float64), to(ts, torch.float64),
+                                             to(ps, torch.float32), self.time_bins, sensor_size=res).transpose(0, 1)
+                             for xs, ys, ts, ps in events])                                  # [L,TB,2,H,W]
+        if win is not None:
+            i, j, th, tw = win
+            stack = stack[..., i:i + th, j:j + tw]
+        if self.noise is not None:
+            stack = add_noise(stack, seed + 3, *self.noise)
+        return {"SeqBlurryF": blur[:, None].contiguous(), "SeqHREv": stack.contiguous(), "RelativeLatentTs": rel_ts.to(dev),
+                "SeqExposureDuty": duty.to(dev)}
+
+
 SUPPORTED_AUGMENT_ORDER = ["RandomCrop", "CenterCrop", "HorizontalFlip", "VertivcalFlip", "Noise", "HotPixel"]
 
 
@@ -368,14 +481,23 @@ def model_inputs(batch):
         yield frame, event, ts[:, [i]].contiguous(), duty, latent[:, i].contiguous()
 
 
-def write_synthetic_clip(path, num_imgs=33, H=64, W=64, events_per_frame=400, seed=0):
-    """A small random clip in the .npz layout (tests, smoke runs of `train_ours.py --data`)."""
+def write_synthetic_clip(path, num_imgs=33, H=64, W=64, events_per_frame=400, seed=0, exposure_stamps=False):
+    """A small random clip in the .npz layout (tests, smoke runs of `train_ours.py --data`).  exposure_stamps: also store
+    `exposure_begin_t` / `exposure_end_t` (int64 microseconds: a shutter period of about 1/240 s, each frame exposed for 10 to
+    90 % of it), which makes the clip readable by RealBlurClipDataset; every other array is the same with and without."""
     g = np.random.RandomState(seed)
     images = g.randint(0, 256, size=(num_imgs, H, W, 3)).astype(np.uint8)
     counts = g.poisson(events_per_frame, size=num_imgs - 1)
     event_idx = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     E = int(event_idx[-1])
     ts = np.sort(g.uniform(0.0, (num_imgs - 1) / 240.0, size=E))
-    np.savez(path, images=images, event_idx=event_idx, xs=g.randint(0, W, size=E).astype(np.int16),
-             ys=g.randint(0, H, size=E).astype(np.int16), ts=ts, ps=(g.randint(0, 2, size=E) * 2 - 1).astype(np.int8))
+    arrays = dict(images=images, event_idx=event_idx, xs=g.randint(0, W, size=E).astype(np.int16),
+                  ys=g.randint(0, H, size=E).astype(np.int16), ts=ts, ps=(g.randint(0, 2, size=E) * 2 - 1).astype(np.int8))
+    if exposure_stamps:          # (drawn after everything else, from a generator of their own: the other arrays do not move)
+        e = np.random.RandomState(seed + 1)
+        period = 1000000 // 240
+        begin = (np.arange(num_imgs) * period + e.randint(0, period // 20, size=num_imgs)).astype(np.int64)
+        arrays.update(exposure_begin_t=begin,
+                      exposure_end_t=begin + e.randint(period // 10, period * 9 // 10, size=num_imgs).astype(np.int64))
+    np.savez(path, **arrays)
     return path

@@ -30,9 +30,21 @@ loss/PerceptualSimilarity/models/weights/v0.1/alex.pth, `--lpips_backbone` torch
 (alexnet-owt-7be5be79.pth) -- by ebfi_amd.lpips on the device, after the timed interval like the others: `lpips` then appears
 in the three yml files and in restored.npz.  Without them the key is left out and stderr says so.
 
-Not done here (out of the hot path's scope): the event visualisations, `--real_blur` clips (a different dataset
-class).  A knob this reader cannot honour is reported on stderr, never dropped silently.  Without --data_list the script runs a
-synthetic clip (BASELINE.json configs 1 / 2 / 5):
+`--real_blur` (the second block of scripts/infer_ours.sh) reads the clips as exposure-stamped recordings of a real camera
+(ebfi_amd.clipdata.RealBlurClipDataset, the counterpart of dataloader/h5dataset_realdata.py): every stored frame is a blurry
+input, its exposure duty comes from the frame's `exposure_begin_t` / `exposure_end_t` stamps, and each load is restored at
+`--interp_num` timestamps `linspace(0, 1, interp_num)`.  Such clips have no sharp ground truth, so nothing is scored: no
+inference.yml / inference_all*.yml, no gt_frame/ directory, --lpips_* unused (stderr says so once).  Both ends of the run are
+device work (ebfi_amd.frameio): a frame is uploaded as uint8 and made planar float by a kernel that also applies the centre
+crop; a load's restored frames are clamped, quantised (the reference's truncating cast, infer_ours.py:135) and interleaved by a
+second kernel, one launch and one download per load.  `restored.npz` then holds `restored_u8` uint8 [loads, interp_num, H, W, 3],
+`blurry_u8` [loads, H, W, 3] (the cast the reference applies to the blurry frame it saves), `exposure_duty`, `timestamps` and
+`period`; --save_float adds the float32 `restored` [loads, interp_num, 3, H, W] (at 260x346 and 256 timestamps that is 276 MB
+per load, hence not the default).  --png writes `img/restored_frame/%09d_%d.png` and `img/blurry_frame/%09d.png` from the uint8
+arrays.
+
+Not done here (out of the hot path's scope): the event visualisations.  A knob this reader cannot honour is
+reported on stderr, never dropped silently.  Without --data_list the script runs a synthetic clip (BASELINE.json configs 1 / 2 / 5):
 
     python infer_ours.py --model_path output/models/Ours/run/checkpoint-iteration99.pth --batch 4 --height 256 --width 256
     python infer_ours.py --batch 1 --height 128 --width 128 --rand-init
@@ -104,6 +116,8 @@ def get_flags(argv=None):
     ap.add_argument("--real_blur", default=False, action="store_true")
     # ---- this implementation's own ----
     ap.add_argument("--png", action="store_true", help="also write the reference's PNG tree (needs PIL)")
+    ap.add_argument("--save_float", action="store_true",
+                    help="with --real_blur: also store the float32 `restored` array in restored.npz (uint8 `restored_u8` only by default)")
     ap.add_argument("--no-metrics", action="store_true",
                     help="with --data_list: do not score the restored frames against the clip's sharp frames (PSNR / SSIM / MSE)")
     ap.add_argument("--lpips_lin", type=str, default=None,
@@ -169,9 +183,11 @@ def dataset_settings(flags):
             ds["ExposureTime"] = None
     if ds["DeblurPretrain"]:
         notes.append("deblur_pretrain: the reference's loop never reads the flag after storing it; ignored here too")
+    ds["real_blur"] = bool(flags.real_blur)
     if flags.real_blur:
-        notes.append("real_blur: the RealBlur-DAVIS dataset class (h5dataset_realdata.py) is not part of the hot path; the clips "
-                     "are read as synthetic-blur clips (periods of sharp frames)")
+        notes.append("real_blur: the clips are read as exposure-stamped recordings (one period per stored frame, the exposure duty "
+                     "from its exposure_begin_t / exposure_end_t stamps, %d timestamps per load); they hold no sharp ground truth, "
+                     "so nothing is scored and no inference*.yml is written" % int(ds["interp_num"]))
     if flags.interp_num is not None and not flags.real_blur:
         notes.append("interp_num only applies to --real_blur in the reference; ignored")
     return ds, notes
@@ -311,6 +327,68 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, me
     return iF + 1, spent, (result, step)
 
 
+def write_png_u8(path, hwc):
+    from PIL import Image
+    Image.fromarray(hwc).save(path)
+
+
+@torch.no_grad()
+def infer_clip_real(interp, data_path, ds_cfg, root_path, device, seed, png=False, save_float=False):
+    """infer_body of the reference with real_blur (infer_ours.py:81-118, :135-138) for one clip: every sequence of the dataset
+    is one item, every load of it one frame, every load restored at the interp_num timestamps; nothing is scored.  Returns
+    (frames written, seconds inside the model)."""
+    from ebfi_amd import clipdata
+    from ebfi_amd.frameio import planar_to_u8
+    name = os.path.basename(data_path)
+    data = clipdata.RealBlurClipDataset(data_path, time_bins=int(ds_cfg["time_bins"]), interp_num=int(ds_cfg["interp_num"]),
+                                        periods_per_seq=ds_cfg["NumPeriodPerSeq"], sliding_window_seq=ds_cfg["SlidingWindowSeq"],
+                                        periods_per_load=ds_cfg["NumPeriodPerLoad"], sliding_window_load=ds_cfg["SlidingWindowLoad"],
+                                        crop=ds_cfg["center_crop"], device=device,
+                                        noise=(ds_cfg["noise"]["noise_std"], ds_cfg["noise"]["noise_fraction"]) if ds_cfg["noise"]["enabled"] else None)
+    img_path = os.path.join(root_path, "img")
+    os.makedirs(root_path, exist_ok=False)                # (like the reference: an existing result is never overwritten)
+    if png:
+        for sub in ("blurry_frame", "restored_frame"):
+            os.makedirs(os.path.join(img_path, sub), exist_ok=False)
+    restored_u8, restored, blurry_u8, duties, stamps, loads = [], [], [], [], [], []
+    iL = iF = -1
+    spent = 0.0
+    for si, seq in enumerate(data.items):
+        item = data.__getitem__(si, seed=seed + 7919 * si + seq[0][0])
+        for idxL, (left, right) in enumerate(seq):
+            iL += 1
+            frame = item["SeqBlurryF"][idxL]               # [1(NumP), 3, H, W] -> batch of one
+            event = item["SeqHREv"][idxL:idxL + 1]         # [1, TB, 2, H, W]
+            ts = item["RelativeLatentTs"][idxL, 0]         # [interp_num]
+            duty = item["SeqExposureDuty"][idxL]           # [1, 1]
+            torch.cuda.synchronize(device)
+            t0 = time.perf_counter()
+            pred = interp(frame.contiguous(), event.contiguous(), duty.contiguous(), [float(v) for v in ts.tolist()])
+            torch.cuda.synchronize(device)
+            spent += time.perf_counter() - t0
+            u8 = planar_to_u8(pred[0]).cpu().numpy()        # [interp_num, H, W, 3]: one launch, one download per load
+            b8 = planar_to_u8(frame).cpu().numpy()[0]      # (infer_ours.py:137: the same cast on the blurry frame)
+            restored_u8.append(u8)
+            if save_float:
+                restored.append(pred[0].cpu().numpy())
+            blurry_u8.append(b8)
+            duties.append(float(duty.item()))
+            stamps.append(ts.cpu().numpy())
+            loads.append(left)
+            for i in range(u8.shape[0]):
+                iF += 1
+                if png:
+                    write_png_u8(os.path.join(img_path, "restored_frame", "{:09d}_{}.png".format(iF, iL)), u8[i])
+            if png:
+                write_png_u8(os.path.join(img_path, "blurry_frame", "%09d.png" % iL), b8)
+    if restored_u8:
+        extra = dict(restored=np.stack(restored)) if save_float else {}
+        np.savez(os.path.join(root_path, "restored.npz"), restored_u8=np.stack(restored_u8), blurry_u8=np.stack(blurry_u8),
+                 exposure_duty=np.array(duties, dtype=np.float32), timestamps=np.stack(stamps), period=np.array(loads), **extra)
+    print("%s: %d loads, %d frames restored -> %s" % (name, iL + 1, iF + 1, root_path), flush=True)
+    return iF + 1, spent
+
+
 def run_data_list(flags, interp, device):
     ds_cfg, notes = dataset_settings(flags)
     for n in notes:
@@ -328,7 +406,7 @@ def run_data_list(flags, interp, device):
         except ImportError:
             warn("--png needs PIL, which is not importable: writing restored.npz only")
             png = False
-    metrics = not flags.no_metrics
+    metrics = not flags.no_metrics and not flags.real_blur      # (the real_blur note has said that nothing is scored)
     lpips = None
     if metrics and flags.lpips_lin is not None:
         from ebfi_amd.lpips import load_alex_lpips
@@ -339,6 +417,11 @@ def run_data_list(flags, interp, device):
     frames, spent, results = 0, 0.0, []
     for k, data_path in enumerate(paths):
         print("processing %s" % data_path, flush=True)
+        if flags.real_blur:
+            n, s = infer_clip_real(interp, data_path, ds_cfg, os.path.join(flags.output_path, os.path.basename(data_path)), device,
+                                   seed=flags.data_seed + 100003 * k, png=png, save_float=flags.save_float)
+            frames, spent = frames + n, spent + s
+            continue
         n, s, r = infer_clip(interp, data_path, ds_cfg, os.path.join(flags.output_path, os.path.basename(data_path)), device,
                              seed=flags.data_seed + 100003 * k, png=png, metrics=metrics,
                              info="inference %s on %s" % ([flags.model_path], data_path), lpips=lpips)
@@ -359,9 +442,12 @@ def main(argv=None):
     if (a.lpips_lin is None) != (a.lpips_backbone is None):
         raise SystemExit("infer_ours.py: LPIPS needs both weight files: --lpips_lin (the v0.1 alex.pth heads) and --lpips_backbone "
                          "(torchvision's AlexNet state dict); got only %s" % ("--lpips_lin" if a.lpips_backbone is None else "--lpips_backbone"))
-    if a.lpips_lin is not None and (a.no_metrics or a.data_list is None):
+    if a.lpips_lin is not None and (a.no_metrics or a.data_list is None or a.real_blur):
         warn("--lpips_lin / --lpips_backbone are unused: %s" % ("--no-metrics switches the scoring off" if a.no_metrics
-                                                                 else "only a --data_list run is scored"))
+                                                                 else "only a --data_list run is scored" if a.data_list is None
+                                                                 else "--real_blur clips have no ground truth to score against"))
+    if a.save_float and not (a.real_blur and a.data_list is not None):
+        warn("--save_float only applies to a --real_blur run (the synthetic-blur path always stores the float32 array); ignored")
     torch.manual_seed(a.seed)
     device = torch.device(a.device)
     if device.type != "cuda":

@@ -36,6 +36,8 @@
  *   ebfi_gather_sum             weight re-layouts of the depth-2 Conv3d / ConvTranspose3d (models/model_misc/resnet_3D.py)
  *   ebfi_events_to_stack        dataloader/encodings.py:307-350 (events_to_stack)
  *   ebfi_frame2lap / _frame2dcp myutils/utils.py:34-49 / :15-31
+ *   ebfi_frames_u8_to_planar    GetFrames of the real-data reader (dataloader/h5dataset_realdata.py:178-189) + AugmentData's crop / flips
+ *   ebfi_planar_to_u8           the uint8 image cast of the evaluation loop (infer_ours.py:135)
  *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
  *   ebfi_lpips_*                perceptual_loss(net='alex') of the evaluation loop (loss/restore.py:10-40, LPIPS v0.1)
  *   ebfi_charbonnier_*          CharbonnierLoss of the validation loop (loss/restore.py:95-105, train_ours.py:588)
@@ -80,7 +82,8 @@ extern "C" {
  *      the right arguments, and the binding's version check has nothing new to refuse; later still, as another pure addition
  *      under 14, ebfi_lpips_params_bytes / _pack_params / _workspace / _alex (evaluation LPIPS, AlexNet v0.1); and, again as a
  *      pure addition under 14, ebfi_charbonnier_workspace / _forward / _backward (the validation loop's Charbonnier loss); and
- *      ebfi_duty_head_workspace / _forward / _backward (the duty head and MSE loss of the stage-1 pre-training), likewise */
+ *      ebfi_duty_head_workspace / _forward / _backward (the duty head and MSE loss of the stage-1 pre-training), likewise; and
+ *      ebfi_frames_u8_to_planar / ebfi_planar_to_u8 (the frame upload and download of an inference run on recorded clips) */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -711,6 +714,31 @@ int ebfi_duty_head_forward(const float *ex, const int64_t ex_strides[4], const f
                            void *workspace, int64_t workspace_bytes, float *Ex_out, float *loss_out, void *stream);
 int ebfi_duty_head_backward(const float *g, const float *Ex, const float *duty, int64_t B, int H, int W, float scale,
                             float *grad_ex, void *stream);
+
+/* ------------------------------------------------------------------ frame I/O of an inference run on recorded clips
+ * ebfi_frames_u8_to_planar: n stored frames, interleaved uint8 (pixel (f, Y, X) at src + f * src_strides[0] + Y * src_strides[1]
+ * + X * src_strides[2], its three channels adjacent; frames of H0 x W0 pixels) -> out float32 [n][3][h][w], contiguous:
+ *   out[f][c][y][x] = (float) src[f][i + (flip_v ? h-1-y : y)][j + (flip_h ? w-1-x : x)][reverse_channels ? 2-c : c] / 255.0f
+ * i.e. `torch.from_numpy(frames).permute(0, 3, 1, 2).float() / 255` (dataloader/h5dataset_realdata.py:189) of the window
+ * (i, j, h, w), bit for bit (one correctly rounded fp32 division), with the crop and the flips of AugmentData folded into the
+ * read.  reverse_channels: the BGR -> RGB swap of the synthetic-blur reader (h5dataset.py:296-311); the real-data reader does
+ * not swap.
+ * ebfi_planar_to_u8: in float32 (pixel (f, c, y, x) at in + f * in_strides[0] + c * in_strides[1] + y * in_strides[2] + x)
+ * -> out uint8 [n][H][W][3], contiguous:
+ *   out[f][y][x][c] = (uint8) trunc(min(max(in[f][c][y][x], 0), 1) * 255.0f)
+ * i.e. `(x.clamp(0, 1) * 255).cpu().numpy().transpose(0, 2, 3, 1).astype('uint8')` (infer_ours.py:135) for every finite and
+ * infinite input, bit for bit.  NaN gives 0 (numpy leaves that cast undefined).
+ * Strides in ELEMENTS, int64, >= 0 (the pixel stride of `src` >= 3).  One thread moves four pixels of a row in all three
+ * channels.  The planar side uses 16-byte accesses when its base pointer is 16-byte aligned and the width (and, for `in`, every
+ * stride) is a multiple of 4; the interleaved side uses 4-byte accesses when its base pointer is 4-byte aligned (and, for
+ * `src`, the frame and row strides and j are multiples of 4 and the pixel stride is 3).  Anything else -- a ragged width, a
+ * view that starts mid-row, a byte-offset source -- runs a scalar path with no alignment requirement: the entry point decides
+ * from the actual pointers, nothing is assumed.  One launch on `stream`, no workspace, no host synchronisation: capturable.
+ * Null pointers, n < 0, sizes < 1, a window that leaves the frame, a negative stride -> EBFI_ERR_ARG before anything touches
+ * the GPU; n == 0 is a no-op. */
+int ebfi_frames_u8_to_planar(const uint8_t *src, const int64_t src_strides[3], int64_t n, int H0, int W0, int i, int j, int h,
+                             int w, int reverse_channels, int flip_h, int flip_v, float *out, void *stream);
+int ebfi_planar_to_u8(const float *in, const int64_t in_strides[3], int64_t n, int H, int W, uint8_t *out, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
