@@ -850,22 +850,25 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_data_f32(const float *__restri
     unsigned long long _acc[16] = {0};
     unsigned long long _t0 = __builtin_amdgcn_s_memtime();
 #endif
-    // largest squared column norm of grad_out over the tile's pixels (thread = pixel)
-    float gmax2 = 0.f;
+    // largest column norm of grad_out over the tile's pixels (thread = pixel).  The squares are summed in double: in fp32
+    // they vanish below |grad_out| ~ 2^-75 -- a ZERO bound for a gradient whose contributions are ordinary fp32 numbers, so
+    // the box ran at scale 1 and rounded every one of them to 0 -- and overflow above 2^64, long before the bound does.
+    float gmax = 0.f;
     const int t_ho = y0 + (tid >> 4), t_wo = x0 + (tid & 15);
     const bool t_ok = t_ho < g.Ho && t_wo < g.Wo;
     if (bx.use) {
-        float s2 = 0.f;
+        double s2 = 0.0;
         const unsigned pb = t_ok ? (unsigned)(t_ho * g.Wo + t_wo) * 4u : 0x80000000u;
         for (int co = 0; co < g.Co; ++co) {
-            const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rgo, pb + (unsigned)co * (unsigned)g.HWo * 4u, 0, 0));
-            s2 += v * v;
+            const double v = (double)__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rgo, pb + (unsigned)co * (unsigned)g.HWo * 4u, 0, 0));
+            s2 = fma(v, v, s2);
         }
+        const float gn = (float)sqrt(s2);      // (its rounding is inside the 1.001 of the bound)
         // (fmaxf drops NaN operands: a NaN / Inf column must poison the bound explicitly, or the integer box below would
         // launder it into a finite sum)
-        const int bad = __syncthreads_or(!(s2 <= 3.0e38f));
-        gmax2 = wg_max256(s2, sCG);
-        if (bad) gmax2 = __builtin_nanf("");
+        const int bad = __syncthreads_or(!(gn <= 3.0e38f));
+        gmax = wg_max256(gn, sCG);
+        if (bad) gmax = __builtin_nanf("");
     }
     for (int chunk = 0; chunk < g.nchunks; ++chunk) {
         const Chunk ck = get_chunk(g, chunk);
@@ -931,7 +934,7 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_data_f32(const float *__restri
             float load = (float)cmax;                                                  // exact: counts < 2^24
             wg_max256_2(load, w2, sCG + cells);
             load *= 1.f / 1024.f;
-            const float bound = sqrtf(gmax2) * sqrtf(w2) * mm * load * 1.001f;
+            const float bound = gmax * sqrtf(w2) * mm * load * 1.001f;
             if (bound > 0.f && bound < 3.0e38f) {
                 int e;
                 (void)frexpf(bound, &e);                       // bound = m * 2^e, 0.5 <= m < 1

@@ -24,6 +24,13 @@
  *     is what this file iterates directly (the extra window cells always carry weight 0);
  *   - grad_mask does not include the mask factor, grad_offset does.
  *
+ * One deliberate difference: a NaN sampling position.  The reference's im2col excludes it (its
+ * rule is the positive form above, which a NaN fails), but its col2im_coord tests the negated
+ * form, which a NaN passes, and then indexes the image with floor(NaN): undefined, an
+ * out-of-bounds read in practice.  Here the positive form is used everywhere, so a NaN tap is
+ * excluded from every gradient and contributes exact zeros; finite and infinite positions are
+ * treated exactly as in the reference.
+ *
  * The reference's C++ cannot be built in this image (it includes TH/TH.h and THC headers that
  * torch 2.10 no longer ships), so this restatement is pinned by the reference's own
  * known-answer tests (models/DCNv2/testcpu.py:32-67 zero-offset identity, :69-97 gradcheck),
@@ -192,6 +199,10 @@ static void FN(col2im_1)(const FN(dcn_geom) *g, const REAL *colg, const REAL *of
                         const REAL fh = h_in + i * g->dh + dy;
                         const REAL fw = w_in + j * g->dw + dx;
                         const REAL top = colg[(size_t)(c * kk + t) * HWo + p] * m;
+                        /* pixel_weight() is 0 for every such sample; skipped before the int
+                         * conversion, which is undefined for NaN / Inf / |fh| >= 2^31 */
+                        if (!(fh > -1 && fw > -1 && fh < g->H && fw < g->W))
+                            continue;
                         const int ch = (int)fh, cw = (int)fw; /* C truncation, as the reference */
                         for (int ddy = -2; ddy <= 2; ++ddy)
                             for (int ddx = -2; ddx <= 2; ++ddx) {
@@ -232,7 +243,9 @@ static void FN(col2im_coord_1)(const FN(dcn_geom) *g, const REAL *colg, const RE
                         const REAL cg = colg[(size_t)(c * kk + t) * HWo + p];
                         REAL fh = h_in + i * g->dh + dy;
                         REAL fw = w_in + j * g->dw + dx;
-                        if (fh <= -1 || fw <= -1 || fh >= g->H || fw >= g->W) {
+                        /* the validity rule in im2col's positive form: a NaN position is
+                         * excluded here too (see the header) */
+                        if (!(fh > -1 && fw > -1 && fh < g->H && fw < g->W)) {
                             fh = fw = -2;
                         } else {
                             mval += cg * FN(bilinear)(plane, g->H, g->W, fh, fw);

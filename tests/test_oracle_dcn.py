@@ -118,6 +118,66 @@ def test_forward_backward_vs_grid_sample(cfg):
         assert torch.allclose(a, b, atol=1e-9), name
 
 
+def _edge_rel(a, b):
+    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
+
+
+def _edge_names():
+    import test_gpu_dcn_edges as edges
+    return edges.NAMES
+
+
+@pytest.mark.parametrize("name", _edge_names())
+def test_edge_case_builders_are_resolved_by_the_oracle_itself(name):
+    """CPU companion of tests/test_gpu_dcn_edges.py (same builders, identical tensors).  For every scenario the oracle's
+    float32 backward agrees with its float64 backward within the 5e-5 the GPU tests use, so the reference alone stays inside
+    the bar on these inputs (non-finite results, which only the inf in grad_out of 4(d) produces: same cells, the rest within
+    the bar).  For scenarios 1 and 3, grad_input, grad_mask and grad_weight also match autograd
+    through the independent grid_sample statement above; grad_offset is left out, its one-sided convention at integer
+    positions being the reference's own."""
+    import test_gpu_dcn_edges as edges
+    case = edges.build(name)
+    out32, g32 = edges.oracle(case, torch.float32)
+    out64, g64 = edges.oracle(case, torch.float64)
+    keep = [torch.ones_like(r, dtype=torch.bool) for r in g64]
+    if name.startswith("2-"):      # NaN taps are excluded by the oracle: every gradient finite, compared everywhere
+        assert all(torch.isfinite(r).all() for r in g64)
+    if name.startswith("4d-"):
+        assert not torch.isfinite(g64[0]).all()
+        for i, r in enumerate(g64):
+            assert torch.equal(torch.isfinite(r), torch.isfinite(g32[i])), edges.GRADS[i]
+            keep[i] = torch.isfinite(r)
+    assert torch.isfinite(out64).all() and torch.isfinite(out32).all()
+    assert _edge_rel(out32.double(), out64) < edges.FWD_BAR
+    if name.startswith("4b-"):
+        k = int(name.rsplit("-k", 1)[1])
+        assert edges.scaled_reference_is_normal(edges.oracle(edges.build(name.rsplit("-k", 1)[0] + "-k0"), torch.float64)[1], k)
+    for a, r, k, n in zip(g32, g64, keep, edges.GRADS):
+        assert _edge_rel(a[k].double(), r[k]) < edges.GRAD_BAR, n
+    if name[0] in "13":
+        cfg = case.cfg
+        t = [v.double().requires_grad_() for v in (case.x, case.off, case.msk, case.w, case.b)]
+        ref = dcn_grid_sample(*t, cfg["s"], cfg["p"], cfg["d"], cfg["dg"])
+        assert _edge_rel(out64, ref.detach()) < 1e-12
+        gx, gm, gw = torch.autograd.grad(ref, (t[0], t[2], t[3]), case.g.double())
+        for a, r, n in ((g64[0], gx, "input"), (g64[2], gm, "mask"), (g64[3], gw, "weight")):
+            assert _edge_rel(a, r) < 1e-12, n
+
+
+def test_nan_position_is_excluded_from_every_gradient():
+    """The one deliberate difference from the reference (oracle/dcn_ref_impl.h): a NaN sampling position fails the validity
+    rule in its positive form everywhere, so it behaves like an infinite one -- exact zeros, no floor(NaN) indexing."""
+    import test_gpu_dcn_edges as edges
+    case = edges.build("2-W1")
+    as_inf = case._replace(off=torch.where(torch.isnan(case.off), torch.tensor(float("inf")), case.off))
+    for dt in (torch.float32, torch.float64):
+        (o1, g1), (o2, g2) = edges.oracle(case, dt), edges.oracle(as_inf, dt)
+        assert torch.equal(o1, o2)
+        for a, b in zip(g1, g2):
+            assert torch.isfinite(a).all() and torch.equal(a, b)
+        assert (g1[1][edges.nan_taps(case)] == 0).all()
+
+
 def test_integer_offsets_on_grid():
     """Sample positions exactly on grid points / exactly at -1 and H: the strict inequalities."""
     x = torch.arange(16, dtype=torch.float32).view(1, 1, 4, 4) + 1
