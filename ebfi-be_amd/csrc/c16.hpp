@@ -16,6 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "scale_law.hpp"
+
 namespace ebfi {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -50,7 +52,7 @@ __device__ __forceinline__ void saturate_fp16_conversions(bool on = true) { __bu
 // after the first iteration, never showed it).  A step whose values all stay below the floor keeps its scale (the true
 // maximum is within 1/8 of the previous one) and lets the floor decay.
 constexpr int SLOT_STRIDE = 64, SLOT_AMAX = 32, SLOT_FLOOR = 1;
-constexpr int F16_TARGET_EXP = 2;          // next scale: |max| * scale in [2^(F16_TARGET_EXP-1), 2^F16_TARGET_EXP) (f16scale.TARGET_EXP)
+// (F16_TARGET_EXP and the rest of the slot law -- when a wave reports, what the finish launch makes of a slot: scale_law.hpp)
 // Running |max| of staged values, taken on the float BITS: non-negative floats order like unsigned integers and every NaN
 // pattern orders above +inf, so ONE NaN element survives into the slot and raises the guard -- fmaxf returns its non-NaN
 // operand and would drop it (round-4 advisory: with saturating conversions the recorded maximum is the only overflow signal).
@@ -70,7 +72,7 @@ struct ScaleSlot {
         for (int d = 32; d >= 1; d >>= 1) m = amax_acc(m, __shfl_xor(m, d, 64));
         // (many workgroups report into one word: only a value above the one already there needs the atomic -- NaN compares
         // false and goes through)
-        if (p && (threadIdx.x & 63) == 0 && !(m <= fmaxf(__builtin_nontemporal_load(p + SLOT_AMAX), p[SLOT_FLOOR])))
+        if (p && (threadIdx.x & 63) == 0 && should_report(m, __builtin_nontemporal_load(p + SLOT_AMAX), p[SLOT_FLOOR]))
             atomicMax(reinterpret_cast<unsigned *>(p + SLOT_AMAX), __float_as_uint(m));
     }
 };

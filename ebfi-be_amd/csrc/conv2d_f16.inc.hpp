@@ -716,24 +716,12 @@ __global__ __launch_bounds__(256) void f16_scales_finish_kernel(float *__restric
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float *slot = slots + (int64_t)SLOT_STRIDE * i;
-    const float a = slot[SLOT_AMAX], s = slot[0];
-    if (!(a > 0.f)) {                      // nothing staged through this slot, or nothing above the floor: keep the scale
-        if (a != a) atomicOr(flag, 1);
-        slot[SLOT_AMAX] = 0.f;
-        slot[SLOT_FLOOR] *= 0.5f;          // (decays fast: a tensor that shrank is measured again within a few steps)
-        return;
-    }
-    if (!(a <= 3.0e38f) || a * s > 60000.f) atomicOr(flag, 1);
-    if (a <= 3.0e38f) {
-        int e;
-        (void)frexpf(a, &e);               // a = m * 2^e, m in [0.5, 1)
-        // (clamped like the host-side calibration, f16scale.calibrate: a recorded |max| below ~2^-125 must not turn the
-        // next scale into +inf -- the x0.1 initialisation does produce 1e-29 gradients)
-        slot[0] = ldexpf(1.f, min(F16_TARGET_EXP - e, 120));
-        slot[SLOT_FLOOR] = 0.875f * a;     // next step: only waves above 7/8 of this maximum report (c16.hpp)
-    } else {
-        slot[SLOT_FLOOR] = 0.f;
-    }
+    // (the law itself -- keep / next scale, floor, flag -- is finish_slot of scale_law.hpp, shared with the host: the exponent
+    // clamp at 120 is the one f16scale.next_scale applies, so host calibration and this launch give the same scale bit for bit)
+    const SlotUpdate u = finish_slot(slot[SLOT_AMAX], slot[0], slot[SLOT_FLOOR]);
+    if (u.flag) atomicOr(flag, 1);
+    slot[0] = u.scale;
+    slot[SLOT_FLOOR] = u.floor;
     slot[SLOT_AMAX] = 0.f;
 }
 
@@ -754,7 +742,7 @@ __global__ __launch_bounds__(256) void pack_table_f16_kernel(const float *__rest
     unsigned m = __float_as_uint(fabsf(v));
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d, 64));
-    if ((threadIdx.x & 63) == 0 && !(__uint_as_float(m) <= fmaxf(__builtin_nontemporal_load(slot + SLOT_AMAX), slot[SLOT_FLOOR])))
+    if ((threadIdx.x & 63) == 0 && should_report(__uint_as_float(m), __builtin_nontemporal_load(slot + SLOT_AMAX), slot[SLOT_FLOOR]))
         atomicMax(reinterpret_cast<unsigned *>(slot + SLOT_AMAX), m);
 }
 

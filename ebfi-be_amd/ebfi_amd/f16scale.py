@@ -3,19 +3,22 @@
 The data gradient and the weight gradient of the training step run one fp16 MFMA per product.  fp16 has the significand
 the parity bar needs (11 bits: the packed gradient moves from 0.95e-3 to 1.09e-3 of the oracle's) but
 not the range: with the reference's x0.1 initialisation (model_util.py:16-36) gradients fall to 1e-29 in the early layers.
-Every operand tensor of those kernels therefore has a SLOT of two device floats {scale, running |max|}:
+Every operand tensor of those kernels therefore has a SLOT of device floats {scale, floor, running |max|} (the law of a slot
+is stated once, in csrc/scale_law.hpp; DESIGN.md section 4 has the table):
 
   * the kernel multiplies what it stages by `scale` (a power of two: exact in fp32) and raises `|max|` atomically,
   * `finish()` -- one tiny launch after the backward pass, captured with the step's graph -- sets every slot's next scale so
-    that |max| * scale lies in [2, 4) (14 binades of headroom to fp16's 65504; below, fp16 keeps 11 bits down to 2^-14 and
-    the matrix cores take subnormal operands: measured, the result's error is flat until |max| * scale < 2^-10),
+    that |max| * scale lies in [2, 4) (the scale itself at most 2^120; 14 binades of headroom to fp16's 65504; below, fp16
+    keeps 11 bits down to 2^-14 and the matrix cores take subnormal operands: measured, the result's error is flat until
+    |max| * scale < 2^-10),
     clears the maxima and raises the GUARD flag when a value was not finite or could have overflowed; the guarded Adam
     launch then skips the update of that step (guard[1] counts such steps),
   * the FIRST use of a slot is calibrated just in time from the tensor itself (`calibrate`: torch reductions on the launch
-    stream, no host synchronisation) -- that is the first eager pass of a run, before any graph is captured.  The engine
-    repeats that for every slot during the first `Engine.calibration_steps` (2) optimiser steps of a run: from the x0.1
-    initialisation the first Adam update moves activations by fourteen decades (biases 0 -> 1e-4 against 1e-18 signals),
-    which no one-step-old scale survives (measured with tools/scaletrace.py: steps 1-4 skipped without it, none with it),
+    stream, no host synchronisation; `next_scale`, the same law as the finish launch bit for bit) -- that is the first
+    eager pass of a run, before any graph is captured.  The engine repeats that for every slot during the first
+    `Engine.calibration_steps` (2) optimiser steps of a run: from the x0.1 initialisation the first Adam update moves
+    activations by fourteen decades (biases 0 -> 1e-4 against 1e-18 signals), which no one-step-old scale survives
+    (measured with tools/scaletrace.py: steps 1-4 skipped without it, none with it),
   * the kernels convert with MODE.FP16_OVFL set: a value past the range saturates at 65504 instead of becoming inf, so one
     stale scale does not turn every maximum recorded further down the backward chain into inf (a repair per layer per step).
 
@@ -30,8 +33,21 @@ from . import _native as N
 
 _ACTIVE = None
 TARGET_EXP = 2                      # |max| * scale in [2^(TARGET_EXP-1), 2^TARGET_EXP)
+SCALE_EXP_MAX = 120                 # ... but no scale above 2^120 (csrc/scale_law.hpp): an |max| below 2^-118 keeps that one
 SLOT_STRIDE, SLOT_AMAX = 64, 32     # floats per slot; offset of the running |max| (csrc/c16.hpp: separate cache lines)
 SLOT_FLOOR = 1                      # floor of the running |max| (7/8 of the previous step's: waves below it send no atomic)
+
+
+def next_scale(amax):
+    """The scale that puts `amax` (an fp32 tensor of maxima, any shape, any device) into [2^(TARGET_EXP-1), 2^TARGET_EXP):
+    2^(TARGET_EXP - e) for amax = m * 2^e with m in [0.5, 1), the exponent held at SCALE_EXP_MAX -- bit for bit what
+    f16_scales_finish_kernel sets from a recorded maximum (csrc/scale_law.hpp finish_slot).  amax == 0 or not finite: 1."""
+    amax = amax.float()
+    ok = (amax > 0) & torch.isfinite(amax)
+    _, e = torch.frexp(torch.where(ok, amax, torch.ones_like(amax)))          # exact at every magnitude, subnormals included
+    k = (TARGET_EXP - e.to(torch.int32)).clamp(max=SCALE_EXP_MAX)             # in [-126, 120]: a normal power of two,
+    scale = ((k + 127) << 23).view(torch.float32)                             # written as its bits (no pow / exp2 rounding)
+    return torch.where(ok, scale, torch.ones_like(amax))
 
 
 def active_book():
@@ -87,8 +103,7 @@ class ScaleBook:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("ScaleBook: slot %d met for the first time inside a graph capture; run one eager pass first" % i)
         amax = torch.stack([t.detach().abs().amax().float() for t in tensors]).amax()
-        e = torch.floor(torch.log2(amax.clamp_min(1e-37))) + 1.0          # amax = m * 2^e, m in [0.5, 1)
-        scale = torch.where((amax > 0) & torch.isfinite(amax), torch.exp2(TARGET_EXP - e), torch.ones_like(amax))
+        scale = next_scale(amax)
         self.slots[SLOT_STRIDE * i:SLOT_STRIDE * i + 1].copy_(scale.reshape(1))
         self.calibrated.add(i)
 
