@@ -17,7 +17,11 @@ order (infer_ours.py:82-118) with `model(Frame, Event, T, GTEx)[-1]` per timesta
 timestamp-independent prefix once per load, the rest replayed from a hipGraph; bit-identical to the per-timestamp call) and
 writes, per clip, `<output_path>/<clip name>/restored.npz` (`restored` float32 [loads, NumF, 3, H, W], `blurry`,
 `exposure_duty`, `timestamps`) and -- with --png, when PIL is importable -- the reference's image tree
-`<clip name>/img/{restored_frame/%09d_%d.png, blurry_frame/%09d.png, gt_frame/%09d_%d.png}`.
+`<clip name>/img/{restored_frame/%09d_%d.png, blurry_frame/%09d.png, gt_frame/%09d_%d.png}`.  --event_png (PIL again) adds the
+tree's fourth directory, `img/event/{load}_TB{bin:09d}.png`: the reference's event-count image of every time bin of every load
+(infer_ours.py:139-142: plot_event_cnt with 'blue_red', a white background and percentile normalisation), made on the device
+by ebfi_amd.eventvis -- one call over all bins and one download per load, after the timed model interval -- bit-identical to
+the array the reference's function returns; it works with --real_blur too, and --png alone writes what it always wrote.
 
 Every restored timestamp is scored against the clip's sharp frame (infer_ours.py:120-128; --no-metrics switches it off): PSNR,
 SSIM and MSE as loss/restore.py:43-92 and nn.MSELoss define them, computed on the device by ebfi_amd.metrics -- one call per
@@ -43,7 +47,7 @@ second kernel, one launch and one download per load.  `restored.npz` then holds 
 per load, hence not the default).  --png writes `img/restored_frame/%09d_%d.png` and `img/blurry_frame/%09d.png` from the uint8
 arrays.
 
-Not done here (out of the hot path's scope): the event visualisations.  A knob this reader cannot honour is
+Not done here (out of the hot path's scope): the reference's other event plots (3-D clouds, image grids).  A knob this reader cannot honour is
 reported on stderr, never dropped silently.  Without --data_list the script runs a synthetic clip (BASELINE.json configs 1 / 2 / 5):
 
     python infer_ours.py --model_path output/models/Ours/run/checkpoint-iteration99.pth --batch 4 --height 256 --width 256
@@ -116,6 +120,9 @@ def get_flags(argv=None):
     ap.add_argument("--real_blur", default=False, action="store_true")
     # ---- this implementation's own ----
     ap.add_argument("--png", action="store_true", help="also write the reference's PNG tree (needs PIL)")
+    ap.add_argument("--event_png", action="store_true",
+                    help="also write img/event/{load}_TB{bin:09d}.png, the reference's event-count image of every time bin of "
+                         "every load (blue_red, white background, normalised; needs PIL)")
     ap.add_argument("--save_float", action="store_true",
                     help="with --real_blur: also store the float32 `restored` array in restored.npz (uint8 `restored_u8` only by default)")
     ap.add_argument("--no-metrics", action="store_true",
@@ -242,7 +249,7 @@ def summarise_clips(results, info):
 
 
 @torch.no_grad()
-def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, metrics=True, info="", lpips=None):
+def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, metrics=True, info="", lpips=None, event_png=False):
     """infer_body of the reference for one clip: every sequence, every load, every latent timestamp; returns
     (frames written, seconds inside the model, (result, result_step) or None without metrics).  lpips: an
     ebfi_amd.lpips.AlexLPIPS that scores LPIPS as a fourth metric, or None."""
@@ -261,6 +268,8 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, me
     if png:
         for sub in ("blurry_frame", "gt_frame", "restored_frame"):
             os.makedirs(os.path.join(img_path, sub), exist_ok=False)
+    if event_png:
+        os.makedirs(os.path.join(img_path, "event"), exist_ok=False)
     restored, blurry, duties, stamps, loads = [], [], [], [], []
     scores = []                                            # per load: [3 (psnr, ssim, mse) or 4 (+ lpips), NumF]
     track = MetricTracker(["mse", "psnr", "ssim"] + (["lpips"] if lpips is not None else []))
@@ -307,6 +316,8 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, me
                     write_png(os.path.join(img_path, "gt_frame", "{:09d}_{}.png".format(iF, iL)), item["SeqLatentF"][0, 0, i])
             if png:
                 write_png(os.path.join(img_path, "blurry_frame", "%09d.png" % iL), frame[0])
+            if event_png:
+                write_event_pngs(os.path.join(img_path, "event"), iL, event[0])
     if restored:
         extra = {}
         if metrics:
@@ -332,8 +343,17 @@ def write_png_u8(path, hwc):
     Image.fromarray(hwc).save(path)
 
 
+def write_event_pngs(event_dir, iL, stack):
+    """infer_ours.py:139-142 for one load: stack [TB, 2, H, W] on the device -> event/{iL}_TB{idx:09d}.png per time bin.  One
+    native call over all bins, one download."""
+    from ebfi_amd.eventvis import event_count_images
+    imgs = event_count_images(stack, color_scheme="blue_red", black_background=False, is_norm=True).cpu().numpy()
+    for idx in range(imgs.shape[0]):
+        write_png_u8(os.path.join(event_dir, "{}_TB{:09d}.png".format(iL, idx)), imgs[idx])
+
+
 @torch.no_grad()
-def infer_clip_real(interp, data_path, ds_cfg, root_path, device, seed, png=False, save_float=False):
+def infer_clip_real(interp, data_path, ds_cfg, root_path, device, seed, png=False, save_float=False, event_png=False):
     """infer_body of the reference with real_blur (infer_ours.py:81-118, :135-138) for one clip: every sequence of the dataset
     is one item, every load of it one frame, every load restored at the interp_num timestamps; nothing is scored.  Returns
     (frames written, seconds inside the model)."""
@@ -350,6 +370,8 @@ def infer_clip_real(interp, data_path, ds_cfg, root_path, device, seed, png=Fals
     if png:
         for sub in ("blurry_frame", "restored_frame"):
             os.makedirs(os.path.join(img_path, sub), exist_ok=False)
+    if event_png:
+        os.makedirs(os.path.join(img_path, "event"), exist_ok=False)
     restored_u8, restored, blurry_u8, duties, stamps, loads = [], [], [], [], [], []
     iL = iF = -1
     spent = 0.0
@@ -381,6 +403,8 @@ def infer_clip_real(interp, data_path, ds_cfg, root_path, device, seed, png=Fals
                     write_png_u8(os.path.join(img_path, "restored_frame", "{:09d}_{}.png".format(iF, iL)), u8[i])
             if png:
                 write_png_u8(os.path.join(img_path, "blurry_frame", "%09d.png" % iL), b8)
+            if event_png:
+                write_event_pngs(os.path.join(img_path, "event"), iL, event[0])
     if restored_u8:
         extra = dict(restored=np.stack(restored)) if save_float else {}
         np.savez(os.path.join(root_path, "restored.npz"), restored_u8=np.stack(restored_u8), blurry_u8=np.stack(blurry_u8),
@@ -399,13 +423,14 @@ def run_data_list(flags, interp, device):
     os.makedirs(flags.output_path, exist_ok=True)
     from ebfi_amd import clipdata
     paths = clipdata.list_clips(flags.data_list) if flags.data_list.endswith(".txt") else [flags.data_list]
-    png = flags.png
-    if png:
+    png, event_png = flags.png, flags.event_png
+    if png or event_png:
         try:
             import PIL  # noqa: F401
         except ImportError:
-            warn("--png needs PIL, which is not importable: writing restored.npz only")
-            png = False
+            warn("%s needs PIL, which is not importable: writing restored.npz only"
+                 % " / ".join(f for f, on in (("--png", png), ("--event_png", event_png)) if on))
+            png = event_png = False
     metrics = not flags.no_metrics and not flags.real_blur      # (the real_blur note has said that nothing is scored)
     lpips = None
     if metrics and flags.lpips_lin is not None:
@@ -419,12 +444,14 @@ def run_data_list(flags, interp, device):
         print("processing %s" % data_path, flush=True)
         if flags.real_blur:
             n, s = infer_clip_real(interp, data_path, ds_cfg, os.path.join(flags.output_path, os.path.basename(data_path)), device,
-                                   seed=flags.data_seed + 100003 * k, png=png, save_float=flags.save_float)
+                                   seed=flags.data_seed + 100003 * k, png=png, save_float=flags.save_float,
+                                   event_png=event_png)
             frames, spent = frames + n, spent + s
             continue
         n, s, r = infer_clip(interp, data_path, ds_cfg, os.path.join(flags.output_path, os.path.basename(data_path)), device,
                              seed=flags.data_seed + 100003 * k, png=png, metrics=metrics,
-                             info="inference %s on %s" % ([flags.model_path], data_path), lpips=lpips)
+                             info="inference %s on %s" % ([flags.model_path], data_path), lpips=lpips,
+                             event_png=event_png)
         frames, spent = frames + n, spent + s
         if r is not None:
             results.append((os.path.basename(data_path),) + r)
@@ -446,6 +473,8 @@ def main(argv=None):
         warn("--lpips_lin / --lpips_backbone are unused: %s" % ("--no-metrics switches the scoring off" if a.no_metrics
                                                                  else "only a --data_list run is scored" if a.data_list is None
                                                                  else "--real_blur clips have no ground truth to score against"))
+    if a.event_png and a.data_list is None:
+        warn("--event_png only applies to a --data_list run (the synthetic mode writes no files); ignored")
     if a.save_float and not (a.real_blur and a.data_list is not None):
         warn("--save_float only applies to a --real_blur run (the synthetic-blur path always stores the float32 array); ignored")
     torch.manual_seed(a.seed)

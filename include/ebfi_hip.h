@@ -38,6 +38,8 @@
  *   ebfi_frame2lap / _frame2dcp myutils/utils.py:34-49 / :15-31
  *   ebfi_frames_u8_to_planar    GetFrames of the real-data reader (dataloader/h5dataset_realdata.py:178-189) + AugmentData's crop / flips
  *   ebfi_planar_to_u8           the uint8 image cast of the evaluation loop (infer_ours.py:135)
+ *   ebfi_event_cnt_image        event_visualisation.plot_event_cnt of the evaluation loop (infer_ours.py:139-142,
+ *                               myutils/vis_events/matplotlib_plot_events.py:127-251)
  *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
  *   ebfi_lpips_*                perceptual_loss(net='alex') of the evaluation loop (loss/restore.py:10-40, LPIPS v0.1)
  *   ebfi_charbonnier_*          CharbonnierLoss of the validation loop (loss/restore.py:95-105, train_ours.py:588)
@@ -83,7 +85,8 @@ extern "C" {
  *      under 14, ebfi_lpips_params_bytes / _pack_params / _workspace / _alex (evaluation LPIPS, AlexNet v0.1); and, again as a
  *      pure addition under 14, ebfi_charbonnier_workspace / _forward / _backward (the validation loop's Charbonnier loss); and
  *      ebfi_duty_head_workspace / _forward / _backward (the duty head and MSE loss of the stage-1 pre-training), likewise; and
- *      ebfi_frames_u8_to_planar / ebfi_planar_to_u8 (the frame upload and download of an inference run on recorded clips) */
+ *      ebfi_frames_u8_to_planar / ebfi_planar_to_u8 (the frame upload and download of an inference run on recorded clips); and
+ *      ebfi_event_cnt_image_workspace / ebfi_event_cnt_image (the event-count images of the evaluation loop), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -739,6 +742,39 @@ int ebfi_duty_head_backward(const float *g, const float *Ex, const float *duty, 
 int ebfi_frames_u8_to_planar(const uint8_t *src, const int64_t src_strides[3], int64_t n, int H0, int W0, int i, int j, int h,
                              int w, int reverse_channels, int flip_h, int flip_v, float *out, void *stream);
 int ebfi_planar_to_u8(const float *in, const int64_t in_strides[3], int64_t n, int H, int W, uint8_t *out, void *stream);
+
+/* ------------------------------------------------------------------ event-count images of the evaluation loop
+ * ebfi_event_cnt_image: n images of two polarity planes, float32 (value (f, p, y, x) at ev + f * ev_strides[0] + p * ev_strides[1]
+ * + y * ev_strides[2] + x; p = 0 positive, 1 negative) -> out uint8 [n][H][W][3], contiguous: for every image what
+ *   event_visualisation().plot_event_cnt(ev[f].transpose(1, 2, 0), False, color_scheme=..., use_opencv=..., is_black_background=...,
+ *                                        is_norm=...)
+ * returns (myutils/vis_events/matplotlib_plot_events.py:127-251; infer_ours.py:139-142 calls it once per time bin of a load with
+ * SeqHREv[0], 'blue_red', a white background and normalisation), bit for bit for every finite float32 input: negative values,
+ * denormals and values spanning many exponents included, not only counts.
+ * With is_norm the planes are normalised by np.percentile(plane, 1) and np.percentile(plane, 99) of both polarities.  Each
+ * percentile interpolates two adjacent order statistics; the four per plane are found exactly by a three-pass (11 + 11 + 10 bit)
+ * radix select over an order-preserving integer key of the float, with integer histograms in LDS merged by integer adds, so the
+ * result does not depend on arrival order; the ranks and weights (numpy's 'linear' method as it behaves for a float32 array)
+ * are host arithmetic from H * W, and one device thread per plane interpolates in numpy's operation order.  Without is_norm
+ * no percentile is needed and none is computed: one launch.  The colour map follows the reference's evaluation order and
+ * types (fp32 normalisation with one correctly rounded division, clip, masks, `1 - x` in fp32, `* 255` and the truncating cast
+ * in double); the reference's final BGR -> RGB reversal is folded into the store and omitted when use_opencv is set.
+ * color_scheme: EBFI_EVENT_BLUE_RED or EBFI_EVENT_GREEN_RED.  EBFI_EVENT_GRAY -> EBFI_ERR_UNSUPPORTED: in the reference it only
+ * runs with use_opencv=True (cv2.cvtColor refuses its two-dimensional canvas otherwise) and nothing calls it.
+ * Strides in ELEMENTS, int64, >= 0; the column stride is 1.  16-byte loads when W % 4 == 0, `ev` is 16-byte aligned and every
+ * stride is a multiple of 4, dword stores when `out` is 4-byte aligned as well; anything else runs a scalar path with no
+ * alignment requirement, decided from the actual pointers and strides.
+ * workspace: ebfi_event_cnt_image_workspace(n, H, W, is_norm) bytes (pure host arithmetic; 0 without is_norm, for n == 0 and
+ * for a bad shape), 16-byte aligned, overwritten by every call.  A memset, six small-to-streaming launches and the colour map
+ * go onto `stream` with no host synchronisation between them: capturable.
+ * Null pointers, n < 0, H or W < 1, a negative stride, an unknown scheme, a misaligned workspace -> EBFI_ERR_ARG; a missing or
+ * short workspace -> EBFI_ERR_WORKSPACE; H * W or the launch grid beyond 2^31 - 1 -> EBFI_ERR_UNSUPPORTED; none of them touches
+ * the GPU.  n == 0 is a no-op. */
+enum { EBFI_EVENT_BLUE_RED = 0, EBFI_EVENT_GREEN_RED = 1, EBFI_EVENT_GRAY = 2 };
+int64_t ebfi_event_cnt_image_workspace(int64_t n, int H, int W, int is_norm);
+int ebfi_event_cnt_image(const float *ev, const int64_t ev_strides[3], int64_t n, int H, int W, int color_scheme,
+                         int is_black_background, int is_norm, int use_opencv, uint8_t *out, void *workspace,
+                         int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the

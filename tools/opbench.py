@@ -5,6 +5,8 @@ with device time (hipEvent pairs recorded by libebfi_hip.so on the launch stream
 bytes / flops and the achieved fraction of the MI355X roofline.
 
     python tools/opbench.py [--iters 20] [--B 8] [--hd]
+    python tools/opbench.py --ops eventvis      # the event-count images of a load (TB = 16) at 256x256 and 720x1280, with the
+                                                # host path they replace (download + numpy) timed in the same run
 """
 import argparse
 import json
@@ -33,6 +35,58 @@ def timed(fn, iters, names):
     N.prof_enable(False)
     prof = N.prof_collect()
     return {k: v[1] / max(v[0], 1) for k, v in prof.items() if k in names}, prof
+
+
+def eventvis_lines(iters, TB=16):
+    """ebfi_amd.eventvis.event_count_images over the TB bins of one load (blue_red, white background, normalised: what
+    infer_ours.py --event_png runs).  Device time: hipEvents around whole calls (the memset and all seven launches), and the
+    library's per-kernel times.  Algorithmic bytes: one read of the stack per selection pass made (three), one for the colour
+    map, three bytes written per pixel.  `counts` is the ordinary data (Poisson(0.35) counts: nearly every value falls into
+    one histogram bin); `reals` (normal deviates) spreads over the bins.  The host path it replaces -- the stack's download,
+    then per bin four np.percentile calls and the numpy colour map (tests/eventvis_ref.py) -- is timed once per size."""
+    import time
+
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from eventvis_ref import plot_event_cnt_numpy
+    from ebfi_amd.eventvis import event_count_images
+    names = {"eventvis_hist", "eventvis_select", "eventvis_colour"}
+    lines = []
+    for (h, w) in ((256, 256), (720, 1280)):
+        for kind in ("counts", "reals"):
+            g = torch.Generator(device="cuda").manual_seed(123)
+            ev = (torch.poisson(torch.full((TB, 2, h, w), 0.35, device="cuda"), generator=g) if kind == "counts"
+                  else torch.randn(TB, 2, h, w, device="cuda", generator=g))
+            out = torch.empty(TB, h, w, 3, dtype=torch.uint8, device="cuda")
+            fn = lambda: event_count_images(ev, "blue_red", black_background=False, is_norm=True, out=out)
+            for _ in range(3):
+                fn()
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            start.record()
+            for _ in range(iters):
+                fn()
+            stop.record()
+            torch.cuda.synchronize()
+            ms = start.elapsed_time(stop) / iters
+            per_kernel, prof = timed(fn, iters, names)
+            per_call = {k: round(prof[k][1] / iters, 4) for k in sorted(names) if k in prof}
+            by = TB * h * w * (2 * 4 * (3 + 1) + 3)
+            line = {"op": "eventvis", "data": kind, "TB": TB, "h": h, "w": w, "ms": round(ms, 4), "kernel_ms_per_call": per_call,
+                    "algorithmic_bytes": by, "GBps": round(by / ms / 1e6, 1), "frac_hbm": round(by / ms / 1e6 / HBM_PEAK, 4)}
+            if kind == "counts":
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                host = ev.cpu().numpy()
+                t1 = time.perf_counter()
+                ref = [plot_event_cnt_numpy(host[b].transpose(1, 2, 0), "blue_red", False, False, True, np_percentile=True)
+                       for b in range(TB)]
+                t2 = time.perf_counter()
+                line.update(host_download_ms=round((t1 - t0) * 1e3, 2), host_numpy_ms=round((t2 - t1) * 1e3, 2),
+                            equal_to_host=bool(np.array_equal(np.stack(ref), out.cpu().numpy())))
+            lines.append(line)
+            del ev, out
+    return lines
 
 
 def main():
@@ -121,6 +175,9 @@ def main():
     for l in lines:
         l.update(B=B, h=h, w=w)
         print(json.dumps(l), flush=True)
+    if "eventvis" in a.ops:
+        for l in eventvis_lines(a.iters):
+            print(json.dumps(l), flush=True)
     fwd = [l for l in lines if l["op"] in ("fac_forward", "dcn_forward")]
     if len(fwd) == 2:
         ms = sum(l["ms"] for l in fwd)
