@@ -8,7 +8,9 @@
 //     grad_ev = A_c bl + B_g ev + C_c + atten_c gout[:, :C],      grad_bl = A'_c ev + B'_g bl + C'_c + gout[:, C:]
 // (per-plane coefficients from a tiny double-precision kernel), i.e. one reduction (gout . ev per plane) and one
 // elementwise pass instead of GroupNorm backward x2, the product-mean backward, the concat-stage backward and two
-// 134 MB gradient accumulations.  Sums: fp32 inside a slice, double across slices / channels, fixed order (deterministic).
+// 134 MB gradient accumulations.  The five moments are formed and summed in double from the first element on (the finalisers
+// difference them: E[x^2] - mu^2); the backward's gout . ev dot is fp32 inside a slice, double across slices / channels.
+// Every sum runs in a fixed order (deterministic).
 #include "common.hpp"
 
 using namespace ebfi;
@@ -30,8 +32,8 @@ Plan ed_plan(int64_t planes, int64_t HW) {
     return {(int)ceil_div(HW, chunk), chunk};
 }
 
-template <int NV> __device__ __forceinline__ void block_reduce(float (&v)[NV], float *out) {
-    __shared__ float red[ET / 64][NV];
+template <typename T, int NV> __device__ __forceinline__ void block_reduce(T (&v)[NV], T *out) {
+    __shared__ T red[ET / 64][NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k)
         for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
@@ -41,34 +43,38 @@ template <int NV> __device__ __forceinline__ void block_reduce(float (&v)[NV], f
         for (int k = 0; k < NV; ++k) red[wave][k] = v[k];
     __syncthreads();
     if (threadIdx.x < NV) {
-        float s = 0.f;
+        T s = 0;
         for (int w = 0; w < ET / 64; ++w) s += red[w][threadIdx.x];
         out[threadIdx.x] = s;
     }
 }
 
-// partial[(plane * S + slice) * 5 + {x, xx, z, zz, xz}]
+// partial[(plane * S + slice) * 5 + {x, xx, z, zz, xz}].  Products and sums in double from the first element on: the
+// finalisers form E[x^2] - mu^2 and E[xz] - mu_x mu_z, which cancel an fp32 sum's rounding error up into the leading digits
+// of the variance as soon as |mean| >> std ("ExposureDecision head: accuracy").  Measured at B=8, C=64, 256x256:
+// 43 us with either arithmetic (the 268 MB read paces the pass; timing pairs in the same DESIGN.md subsection).
 __global__ __launch_bounds__(ET) void ed_stats_kernel(const float *__restrict__ x, const float *__restrict__ z,
-                                                      float *__restrict__ partial, int64_t HW, int S, int64_t chunk) {
+                                                      double *__restrict__ partial, int64_t HW, int S, int64_t chunk) {
     const int64_t plane = blockIdx.x / S;
     const int sl = blockIdx.x - (int)(plane * S);
     const int64_t begin = sl * chunk, end = min(HW, begin + chunk);
     const float *px = x + plane * HW, *pz = z + plane * HW;
-    float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int64_t i = begin + threadIdx.x * 4; i < end; i += ET * 4) {
         const float4 a = *reinterpret_cast<const float4 *>(px + i), b = *reinterpret_cast<const float4 *>(pz + i);
-        v[0] += (a.x + a.y) + (a.z + a.w);
-        v[1] += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
-        v[2] += (b.x + b.y) + (b.z + b.w);
-        v[3] += (b.x * b.x + b.y * b.y) + (b.z * b.z + b.w * b.w);
-        v[4] += (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
+        const double ax = a.x, ay = a.y, az = a.z, aw = a.w, bx = b.x, by = b.y, bz = b.z, bw = b.w;
+        v[0] += (ax + ay) + (az + aw);
+        v[1] += (ax * ax + ay * ay) + (az * az + aw * aw);
+        v[2] += (bx + by) + (bz + bw);
+        v[3] += (bx * bx + by * by) + (bz * bz + bw * bw);
+        v[4] += (ax * bx + ay * by) + (az * bz + aw * bw);
     }
-    block_reduce<5>(v, partial + (int64_t)blockIdx.x * 5);
+    block_reduce<double, 5>(v, partial + (int64_t)blockIdx.x * 5);
 }
 
 // stats: [B*C][5] plane means (x, xx, z, zz, xz), then [B*G][4] = (mu_x, rstd_x, mu_z, rstd_z)
 // one workgroup of >= C threads per sample; dynamic LDS: (5 C + 4 G) doubles
-__global__ void ed_fwd_finalize_kernel(const float *__restrict__ partial, const float *__restrict__ gamma,
+__global__ void ed_fwd_finalize_kernel(const double *__restrict__ partial, const float *__restrict__ gamma,
                                        const float *__restrict__ beta, double *__restrict__ stats, float *__restrict__ atten, int B,
                                        int C, int G, int64_t HW, int S, float eps) {
     extern __shared__ double sh[];
@@ -78,10 +84,10 @@ __global__ void ed_fwd_finalize_kernel(const float *__restrict__ partial, const 
     {
         const int b = blockIdx.x;          // one workgroup per sample (samples are independent)
         if (c < C) {
-            const float *pp = partial + ((int64_t)(b * C + c) * S) * 5;
+            const double *pp = partial + ((int64_t)(b * C + c) * S) * 5;
             for (int k = 0; k < 5; ++k) {
                 double s = 0.0;
-                for (int sl = 0; sl < S; ++sl) s += (double)pp[sl * 5 + k];
+                for (int sl = 0; sl < S; ++sl) s += pp[sl * 5 + k];
                 s /= (double)HW;
                 M[c * 5 + k] = s;
                 stats[((int64_t)b * C + c) * 5 + k] = s;
@@ -97,7 +103,11 @@ __global__ void ed_fwd_finalize_kernel(const float *__restrict__ partial, const 
                 mzz += M[j * 5 + 3];
             }
             mx /= cpg, mxx /= cpg, mz /= cpg, mzz /= cpg;
-            const double vx = fmax(mxx - mx * mx, 0.0), vz = fmax(mzz - mz * mz, 0.0);
+            // (not fmax: it would turn the NaN variance of a group that holds an inf into 0, and the attention of the
+            // group's other planes into 0 or 1 where nn.GroupNorm gives NaN)
+            double vx = mxx - mx * mx, vz = mzz - mz * mz;
+            if (vx < 0.0) vx = 0.0;
+            if (vz < 0.0) vz = 0.0;
             grp[c * 4 + 0] = mx;
             grp[c * 4 + 1] = 1.0 / sqrt(vx + (double)eps);
             grp[c * 4 + 2] = mz;
@@ -151,7 +161,7 @@ __global__ __launch_bounds__(ET) void ed_plane_dot_kernel(const float *__restric
         const float4 a = *reinterpret_cast<const float4 *>(px + i), g = *reinterpret_cast<const float4 *>(pg + i);
         v[0] += (a.x * g.x + a.y * g.y) + (a.z * g.z + a.w * g.w);
     }
-    block_reduce<1>(v, partial + blockIdx.x);
+    block_reduce<float, 1>(v, partial + blockIdx.x);
 }
 
 // coef[plane][8] = {A, Bg, Cc, A', Bg', Cc', atten, 0}; grad_gamma / grad_beta summed over samples in order
@@ -249,11 +259,12 @@ __global__ __launch_bounds__(ET) void ed_bwd_apply_kernel(const float *__restric
     }
 }
 
-const char *ed_check(const void *a, const void *b, int B, int C, int64_t HW, int groups) {
+const char *ed_check(const void *a, const void *b, const void *ws, int B, int C, int64_t HW, int groups) {
     if (B <= 0 || C <= 0 || HW <= 0 || groups <= 0) return "bad dimensions";
     if (C % groups || C > 1024) return "channels must divide into the groups and be <= 1024";
     if (HW % 4) return "H*W must be a multiple of 4";
     if (!aligned16(a) || !aligned16(b)) return "maps must be 16-byte aligned";
+    if (!aligned16(ws)) return "workspace must be 16-byte aligned (it holds double partials)";
     return nullptr;
 }
 
@@ -263,20 +274,22 @@ extern "C" size_t ebfi_ed_head_workspace(int B, int C, int64_t HW) {
     if (B <= 0 || C <= 0 || HW <= 0) return 0;
     const int64_t planes = (int64_t)B * C;
     const Plan pl = ed_plan(planes, HW);
-    return (size_t)(planes * pl.slices * 5 + planes * 8) * sizeof(float);
+    // forward: 5 double moments per (plane, slice); backward: one float dot per (plane, slice) in the same space, then the
+    // 8 float coefficients per plane
+    return (size_t)(planes * pl.slices * 5) * sizeof(double) + (size_t)(planes * 8) * sizeof(float);
 }
 
 extern "C" int ebfi_ed_head_forward(const float *ev, const float *bl, const float *gamma, const float *beta, float *out,
                                     float *atten, double *stats, int B, int C, int64_t HW, int groups, float eps, void *workspace,
                                     size_t workspace_bytes, void *stream) {
     if (!ev || !bl || !gamma || !beta || !out || !atten || !stats || !workspace) return fail(EBFI_ERR_ARG, "ed_head_forward: null argument");
-    if (const char *why = ed_check(ev, bl, B, C, HW, groups)) return fail(EBFI_ERR_ARG, "ed_head: %s", why);
+    if (const char *why = ed_check(ev, bl, workspace, B, C, HW, groups)) return fail(EBFI_ERR_ARG, "ed_head: %s", why);
     if (!aligned16(out)) return fail(EBFI_ERR_ARG, "ed_head_forward: out must be 16-byte aligned");
     if (workspace_bytes < ebfi_ed_head_workspace(B, C, HW)) return fail(EBFI_ERR_ARG, "ed_head_forward: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t planes = (int64_t)B * C;
     const Plan pl = ed_plan(planes, HW);
-    float *partial = static_cast<float *>(workspace);
+    double *partial = static_cast<double *>(workspace);
     const unsigned grid = (unsigned)(planes * pl.slices);
     const int fin_threads = (int)(ceil_div(std::max(C, groups), 64) * 64);
     const size_t fin_lds = (size_t)(5 * C + 4 * groups) * sizeof(double);
@@ -302,14 +315,14 @@ extern "C" int ebfi_ed_head_backward(const float *grad_out, const float *ev, con
                                      void *stream) {
     if (!grad_out || !ev || !bl || !gamma || !beta || !atten || !stats || !grad_ev || !grad_bl || !workspace)
         return fail(EBFI_ERR_ARG, "ed_head_backward: null argument");
-    if (const char *why = ed_check(ev, bl, B, C, HW, groups)) return fail(EBFI_ERR_ARG, "ed_head: %s", why);
+    if (const char *why = ed_check(ev, bl, workspace, B, C, HW, groups)) return fail(EBFI_ERR_ARG, "ed_head: %s", why);
     if (!aligned16(grad_out) || !aligned16(grad_ev) || !aligned16(grad_bl)) return fail(EBFI_ERR_ARG, "ed_head_backward: 16-byte alignment");
     if (workspace_bytes < ebfi_ed_head_workspace(B, C, HW)) return fail(EBFI_ERR_ARG, "ed_head_backward: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t planes = (int64_t)B * C;
     const Plan pl = ed_plan(planes, HW);
     float *partial = static_cast<float *>(workspace);
-    float *coef = partial + planes * pl.slices * 5;
+    float *coef = reinterpret_cast<float *>(static_cast<double *>(workspace) + planes * pl.slices * 5);
     const unsigned grid = (unsigned)(planes * pl.slices);
     const int fin_threads = (int)(ceil_div(std::max(C, groups), 64) * 64);
     const size_t fin_lds = (size_t)(4 * C + 4 * groups) * sizeof(double);

@@ -545,7 +545,8 @@ int ebfi_groupnorm_backward(const float *grad_y, const float *x, const float *ga
  * then (mean, rstd) of both maps per group) for backward, which returns the gradients of the whole head
  *   grad_ev, grad_bl [B,C,H,W], grad_gamma, grad_beta [C] (may be NULL)
  * from grad_out [B,2C,H,W] in one reduction + one elementwise pass (closed form in the moments).
- * HW % 4 == 0, C % groups == 0, C <= 1024; workspace: ebfi_ed_head_workspace(B, C, HW) bytes.  Deterministic. */
+ * HW % 4 == 0, C % groups == 0, C <= 1024; workspace: ebfi_ed_head_workspace(B, C, HW) bytes, 16-byte aligned (it holds
+ * double partial sums).  Deterministic. */
 size_t ebfi_ed_head_workspace(int B, int C, int64_t HW);
 int ebfi_ed_head_forward(const float *ev, const float *bl, const float *gamma, const float *beta, float *out, float *atten,
                          double *stats, int B, int C, int64_t HW, int groups, float eps,
