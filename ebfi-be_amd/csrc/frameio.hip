@@ -3,7 +3,10 @@
 // and the flips of AugmentData folded into the read), and restored planar fp32 frames -> the interleaved uint8 image the
 // reference saves (infer_ours.py:135: `(x.clamp(0, 1) * 255).astype('uint8')`, a truncating cast).
 //
-// Both are pure streaming kernels: one thread owns FOUR consecutive pixels of one row in all three channels, so the planar
+// The training reader's form of the first (period_frames_u8) also writes the blurry input the synthetic-blur dataset feeds,
+// `torch.from_numpy(frames[:e].mean(0)).permute(2, 0, 1).float() / 255` (dataloader/h5dataset.py:311), in the same pass.
+//
+// All are pure streaming kernels: one thread owns FOUR consecutive pixels of one row in all three channels, so the planar
 // side moves as three 16-byte accesses per thread (64 lanes x 16 B = 1 KiB per wave instruction) and the interleaved side as
 // 12 consecutive bytes.  The 16-byte form needs the planar base 16-byte aligned and every planar row start a multiple of four
 // floats; the 4-byte form of the interleaved side needs its base and strides multiples of four bytes.  Both are decided on the
@@ -13,7 +16,9 @@
 // Numerics.  byte / 255.0f is one correctly rounded fp32 division (hipcc's default; the library is built without fast-math
 // flags), which is what the CPU expression computes: bit-identical for all 256 byte values.  The way back is
 // min(max(x, 0), 1) * 255.0f -- one fp32 multiply -- truncated towards zero; NaN maps to 0 (the comparisons below are false
-// for it), which numpy leaves undefined.
+// for it), which numpy leaves undefined.  The blurry mean rounds three times and the kernel rounds in the same places: the byte
+// sum is an exact integer, sum / e is a float64 division (numpy's mean), the quotient is rounded to fp32, and that is divided
+// by 255.0f.  The fused sum / (255 * e) is NOT the same function (e = 3: 167 of the 766 possible sums differ).
 #include "common.hpp"
 
 using namespace ebfi;
@@ -82,6 +87,95 @@ __global__ __launch_bounds__(kThreads) void frames_u8_to_planar(const uint8_t *_
 #pragma unroll
                 for (int c = 0; c < 3; ++c) o[c * plane + k] = (float)p[rev ? 2 - c : c] / 255.0f;
             }
+        }
+    }
+}
+
+// `torch.from_numpy(a[:e].mean(0)).float() / 255` of one sample: the exact integer sum divided by e in float64 (numpy's mean of
+// a uint8 array), rounded to fp32, divided by 255 in fp32 -- three roundings, in this order.
+__device__ inline float blur_mean(uint32_t sum, double n_blur) { return (float)((double)sum / n_blur) / 255.0f; }
+
+// One period of a training item in one pass: sharp [n][3][h][w] as frames_u8_to_planar writes it, and blur [3][h][w], the mean
+// of the first n_blur frames.  A thread owns four pixels of a row (window indexing as above) and walks the n frames, summing
+// the bytes of the first n_blur in integers; every source byte is read once.
+// VEC: w % 4 == 0 and `sharp`, `blur` 16-byte aligned.
+template <bool VEC, bool SRC4>
+__global__ __launch_bounds__(kThreads) void period_frames_u8(const uint8_t *__restrict__ src, int64_t sn, int64_t sh, int64_t sp,
+                                                             int64_t n, int64_t n_blur, int i0, int j0, int h, int w, int rev,
+                                                             int fliph, int flipv, float *__restrict__ sharp,
+                                                             float *__restrict__ blur) {
+    const int quads = (w + kPix - 1) / kPix;
+    const int64_t total = (int64_t)h * quads;
+    const int64_t plane = (int64_t)h * w;
+    const double nb = (double)n_blur;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (int64_t)gridDim.x * kThreads) {
+        const int xq = (int)(t % quads);
+        const int y = (int)(t / quads);
+        const int x = xq * kPix;
+        const int Y = i0 + (flipv ? h - 1 - y : y);
+        const uint8_t *row = src + (int64_t)Y * sh;
+        const int64_t at = (int64_t)y * w + x;
+        uint32_t sum[12];   // [output pixel k][output channel c] at 3 * k + c
+#pragma unroll
+        for (int k = 0; k < 12; ++k) sum[k] = 0;
+        if constexpr (VEC) {
+            const int X0 = fliph ? j0 + w - kPix - x : j0 + x;
+            const uint8_t *p = row + (int64_t)X0 * sp;
+            for (int64_t f = 0; f < n; ++f) {
+                uint8_t b[12];
+                load12<SRC4>(p + f * sn, sp, b);
+                float *o = sharp + f * 3 * plane + at;
+                const uint32_t acc = f < n_blur ? 1u : 0u;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int cs = rev ? 2 - c : c;
+                    const uint8_t b0 = b[3 * (fliph ? 3 : 0) + cs], b1 = b[3 * (fliph ? 2 : 1) + cs];
+                    const uint8_t b2 = b[3 * (fliph ? 1 : 2) + cs], b3 = b[3 * (fliph ? 0 : 3) + cs];
+                    sum[c] += acc * b0;
+                    sum[3 + c] += acc * b1;
+                    sum[6 + c] += acc * b2;
+                    sum[9 + c] += acc * b3;
+                    float4 v;
+                    v.x = (float)b0 / 255.0f;
+                    v.y = (float)b1 / 255.0f;
+                    v.z = (float)b2 / 255.0f;
+                    v.w = (float)b3 / 255.0f;
+                    *reinterpret_cast<float4 *>(o + c * plane) = v;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float4 v;
+                v.x = blur_mean(sum[c], nb);
+                v.y = blur_mean(sum[3 + c], nb);
+                v.z = blur_mean(sum[6 + c], nb);
+                v.w = blur_mean(sum[9 + c], nb);
+                *reinterpret_cast<float4 *>(blur + c * plane + at) = v;
+            }
+        } else {
+            for (int64_t f = 0; f < n; ++f) {
+                float *o = sharp + f * 3 * plane + at;
+                const uint32_t acc = f < n_blur ? 1u : 0u;
+#pragma unroll
+                for (int k = 0; k < kPix; ++k) {
+                    if (x + k < w) {
+                        const int X = j0 + (fliph ? w - 1 - (x + k) : x + k);
+                        const uint8_t *p = row + f * sn + (int64_t)X * sp;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const uint8_t v = p[rev ? 2 - c : c];
+                            sum[3 * k + c] += acc * v;
+                            o[c * plane + k] = (float)v / 255.0f;
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kPix; ++k)
+                if (x + k < w) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) blur[c * plane + at + k] = blur_mean(sum[3 * k + c], nb);
+                }
         }
     }
 }
@@ -173,6 +267,37 @@ extern "C" int ebfi_frames_u8_to_planar(const uint8_t *src, const int64_t src_st
                                reverse_channels, flip_h, flip_v, out);
     }
     return check_launch("frames_u8_to_planar");
+}
+
+extern "C" int ebfi_period_frames_u8(const uint8_t *src, const int64_t src_strides[3], int64_t n, int64_t n_blur, int H0,
+                                     int W0, int i, int j, int h, int w, int reverse_channels, int flip_h, int flip_v,
+                                     float *sharp, float *blur, void *stream) {
+    if (!src || !sharp || !blur || !src_strides) return fail(EBFI_ERR_ARG, "period_frames_u8: null pointer");
+    if (n < 1 || n_blur < 1 || n_blur > n || n_blur > (1 << 24) || H0 < 1 || W0 < 1)   // (255 * n_blur fits the 32-bit sums)
+        return fail(EBFI_ERR_ARG, "period_frames_u8: bad sizes n=%lld n_blur=%lld H0=%d W0=%d (1 <= n_blur <= n)", (long long)n,
+                    (long long)n_blur, H0, W0);
+    if (i < 0 || j < 0 || h < 1 || w < 1 || (int64_t)i + h > H0 || (int64_t)j + w > W0)
+        return fail(EBFI_ERR_ARG, "period_frames_u8: window (%d, %d, %d, %d) outside the %d x %d frame", i, j, h, w, H0, W0);
+    const int64_t sn = src_strides[0], sh = src_strides[1], sp = src_strides[2];
+    if (sn < 0 || sh < 0 || sp < 3) return fail(EBFI_ERR_ARG, "period_frames_u8: strides must be >= 0 (pixel stride >= 3)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool vec = (w % kPix == 0) && aligned16(sharp) && aligned16(blur);
+    const bool src4 = vec && aligned4(src) && sn % 4 == 0 && sh % 4 == 0 && sp == 3 && j % 4 == 0;
+    const int64_t threads = (int64_t)h * ceil_div(w, kPix);
+    const dim3 grid(grid_for(threads)), block(kThreads);
+    {
+        ProfScope ps_("period_frames_u8", st, 0.0, ((double)n * 15.0 + 12.0) * h * w);
+        if (vec && src4)
+            hipLaunchKernelGGL((period_frames_u8<true, true>), grid, block, 0, st, src, sn, sh, sp, n, n_blur, i, j, h, w,
+                               reverse_channels, flip_h, flip_v, sharp, blur);
+        else if (vec)
+            hipLaunchKernelGGL((period_frames_u8<true, false>), grid, block, 0, st, src, sn, sh, sp, n, n_blur, i, j, h, w,
+                               reverse_channels, flip_h, flip_v, sharp, blur);
+        else
+            hipLaunchKernelGGL((period_frames_u8<false, false>), grid, block, 0, st, src, sn, sh, sp, n, n_blur, i, j, h, w,
+                               reverse_channels, flip_h, flip_v, sharp, blur);
+    }
+    return check_launch("period_frames_u8");
 }
 
 extern "C" int ebfi_planar_to_u8(const float *in, const int64_t in_strides[3], int64_t n, int H, int W, uint8_t *out,

@@ -14,6 +14,11 @@ What the reference's H5Dataset does between the file and the network (dataloader
   * crop (random, seeded / centre, both snapped to `scale` like AugmentData :368-411 with scale = 1) and the two flips,
     applied identically to frames and event stacks.
 
+The frames take one of two routes to the same bits (ClipDataset(frames=...)): converted and averaged on the host at full
+resolution, or -- what the trainers use -- the crop window's rows uploaded as uint8 and turned into the sharp planes and the
+blurry mean by one device kernel (ebfi_amd.frameio.period_to_planar).  `batches(..., prefetch=k)` prepares the host half of the
+next k batches on a worker thread while the current one trains.
+
 One item = one period (NumPeriodPerLoad = NumPeriodPerSeq = 1, what config/train_ours.yml trains with); the
 trainer then runs one optimiser pass per latent frame of the batch exactly like train_ours.py:237-251.
 
@@ -39,7 +44,9 @@ second dataset class (dataloader/h5dataset_realdata.py): every stored frame IS a
 there is no sharp ground truth, and the frame reaches the device as uint8 (ebfi_amd.frameio).
 """
 import os
+import queue
 import random
+import threading
 
 import numpy as np
 import torch
@@ -94,11 +101,16 @@ def add_noise(data, seed, noise_std=1.0, noise_fraction=0.1):
     `noise_fraction` of the cells, drawn on the HOST from a generator seeded like the reference seeds torch's global one
     (`torch.manual_seed(seed)`; same engine, same draw order: one normal and one uniform per cell over the contiguous shape) --
     bit-identical counts for the same seed (tests/test_clipdata.py, fixture case 'noise').  The sum is formed on data's device."""
+    return data + draw_noise(tuple(data.shape), seed, noise_std, noise_fraction).to(data.device)
+
+
+def draw_noise(shape, seed, noise_std=1.0, noise_fraction=0.1):
+    """The host half of `add_noise`: the int32 noise counts of a stack of `shape`, a CPU tensor."""
     g = torch.Generator(device="cpu").manual_seed(int(seed))
-    noise = (noise_std * torch.randn(tuple(data.shape), generator=g)).abs().int()
+    noise = (noise_std * torch.randn(tuple(shape), generator=g)).abs().int()
     if noise_fraction < 1.0:
-        noise.masked_fill_(torch.rand(tuple(data.shape), generator=g) >= noise_fraction, 0)
-    return data + noise.to(data.device)
+        noise.masked_fill_(torch.rand(tuple(shape), generator=g) >= noise_fraction, 0)
+    return noise
 
 
 def normalise_events(xs, ys, ts, ps):
@@ -212,11 +224,18 @@ class ClipDataset:
     """Items in the reference's key names and shapes for L = NumPeriodPerLoad = 1 (h5dataset.py:283-295):
         SeqLatentF [1, 1, NumF, 3, H, W]   SeqBlurryF [1, 1, 3, H, W]   SeqHREv [1, TB, 2, H, W]
         RelativeLatentTs [1, 1, NumF]      SeqExposureDuty [1, 1, 1]
-    Frames are produced on the host and moved to `device`; the event stack is binned on the device."""
+    The event stack is binned on the device.  frames="host": the frames are converted and averaged at full resolution on the
+    host, moved to `device` and cropped there.  frames="device": only the crop window's rows of the stored uint8 frames go up,
+    and one kernel (ebfi_amd.frameio.period_to_planar) writes the sharp planes and the blurry mean with the channel reversal,
+    the window and the flips folded into the read -- the same bits, at one byte per sample across the bus.
+
+    An item is made in two halves: `prepare` is host work only (file reads, the staging buffer, the event list, the noise
+    draw) and may run on a worker thread (`batches(..., prefetch=k)`); `finish` issues the uploads and kernels on the calling
+    thread's current stream.  `__getitem__(i, seed)` is `finish(prepare(i, seed))`."""
 
     def __init__(self, paths, time_bins=16, frames_per_period=16, frames_per_blurry=16, exposure_method="Fixed",
                  exposure_time=None, crop=None, crop_mode="random", flips=False, device="cuda", seed=0,
-                 flip_probs=(0.5, 0.5), center_crop=None, noise=None):
+                 flip_probs=(0.5, 0.5), center_crop=None, noise=None, frames="host"):
         """crop / crop_mode: the first crop of AugmentData's list (RandomCrop when enabled, else CenterCrop); center_crop: a
         CenterCrop applied AFTER a random crop when the config enables both (the reference walks its `augment` list in order,
         h5dataset.py:410-433); flip_probs: (horizontal_prob, vertical_prob) of data_augment.flip; noise: None or
@@ -230,6 +249,9 @@ class ClipDataset:
         self.flip_probs, self.center_crop = (float(flip_probs[0]), float(flip_probs[1])), center_crop
         self.noise = None if noise is None else (float(noise[0]), float(noise[1]))
         self.device = torch.device(device)
+        if frames not in ("host", "device"):
+            raise ValueError("frames must be 'host' or 'device', got %r" % (frames,))
+        self.frames = frames
         self.items = []
         for ci, clip in enumerate(self.clips):
             for it in period_items(clip.num_imgs, frames_per_period, frames_per_blurry, exposure_method, exposure_time, seed + ci):
@@ -281,20 +303,87 @@ class ClipDataset:
                 "SeqHREv": stack[None].contiguous(), "RelativeLatentTs": rel_ts[None, None],
                 "SeqExposureDuty": torch.tensor([[[duty]]], dtype=torch.float32, device=dev)}
 
-    def __getitem__(self, index, seed=None):
-        from .encodings import events_to_stack
+    def window(self, resolution, seed):
+        """(i, j, h, w): the crops `augment` applies for this seed, composed into one window of the frame (the whole frame
+        when there is no crop or it is not smaller than the frame)."""
+        H, W = resolution
+        i0 = j0 = 0
+        if self.crop is not None:
+            win = crop_window(H, W, self.crop, self.crop_mode, 1, seed + 2)
+            if win is not None:
+                i0, j0, H, W = win
+        if self.center_crop is not None:
+            win = crop_window(H, W, self.center_crop, "center", 1, seed + 2)
+            if win is not None:
+                i0, j0, H, W = i0 + win[0], j0 + win[1], win[2], win[3]
+        return i0, j0, H, W
+
+    def flip_decisions(self, seed):
+        """(horizontal, vertical) as `augment` decides them for this seed."""
+        if not self.flips:
+            return False, False
+        return random.Random(seed).random() < self.flip_probs[0], random.Random(seed + 1).random() < self.flip_probs[1]
+
+    def stage_frames(self, index, window):
+        """The window's ROWS of the period's stored frames, uint8 [NumF, h, W, 3] as stored (BGR), gathered into a staging
+        buffer: pinned when the device is a GPU (torch's pinned allocator owns it: a block whose upload is still in flight is
+        not handed out again), ordinary memory otherwise."""
+        ci, (latent, _, _) = self.items[index]
+        clip = self.clips[ci]
+        i, _, h, _ = window
+        shape = (len(latent), h, clip.resolution[1], 3)
+        if self.device.type == "cuda":
+            with torch.cuda.device(self.device):          # (a worker thread starts on device 0: pin under the right one)
+                stage = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
+        else:
+            stage = torch.empty(shape, dtype=torch.uint8)
+        rows = stage.numpy()
+        for f, k in enumerate(latent):
+            rows[f] = clip.frame_bgr(k)[i:i + h]
+        return stage
+
+    def prepare(self, index, seed=None):
+        """The host half of an item: no upload, no launch, nothing on a stream (the pinned allocator's own bookkeeping aside),
+        so it may run on a worker thread.  -> what `finish` takes.  The blurry frames are the first `num_blur` of the period's
+        (period_items)."""
         if seed is None:
             seed = random.randint(0, 2 ** 32)
-        sharp, blur, (xs, ys, ts, ps), duty = self.host_item(index)
-        res = self.clips[self.items[index][0]].resolution
-        dev = self.device
+        ci, (_, blurry, duty) = self.items[index]
+        res = self.clips[ci].resolution
+        prepared = {"index": index, "seed": seed, "resolution": res, "duty": duty}
+        if self.frames == "device":
+            win = self.window(res, seed)
+            prepared.update(stage=self.stage_frames(index, win), window=win, num_blur=len(blurry), events=self.event_list(index))
+        else:
+            sharp, blur, events, _ = self.host_item(index)
+            prepared.update(sharp=sharp, blur=blur, events=events)
+        if self.noise is not None:          # (drawn over [L=1, TB, 2, h, w] like the reference)
+            prepared["noise"] = draw_noise((1, self.time_bins, 2) + tuple(self.window(res, seed)[2:]), seed + 3, *self.noise)
+        return prepared
+
+    def finish(self, prepared):
+        """The device half: uploads and kernels on the current stream of the calling thread -> the item dict."""
+        from .encodings import events_to_stack
+        seed, res, dev = prepared["seed"], prepared["resolution"], self.device
+        xs, ys, ts, ps = prepared["events"]
         to = lambda a, dt: torch.from_numpy(a).to(dev, dt)
         stack = events_to_stack(to(xs, torch.float64), to(ys, torch.float64), to(ts, torch.float64), to(ps, torch.float32),
                                 self.time_bins, sensor_size=res).transpose(0, 1)                # [TB,2,H,W]
-        sharp, blur, stack = self.augment([sharp.to(dev), blur.to(dev), stack], res, seed)
-        if self.noise is not None:
-            stack = add_noise(stack[None], seed + 3, *self.noise)[0]          # (drawn over [L=1, TB, 2, H, W] like the reference)
-        return self.assemble(sharp, blur, stack, duty)
+        if self.frames == "device":
+            from .frameio import period_to_planar
+            _, j, h, w = prepared["window"]
+            fh, fv = self.flip_decisions(seed)
+            sharp, blur = period_to_planar(prepared["stage"].to(dev, non_blocking=True), prepared["num_blur"],
+                                           window=(0, j, h, w), reverse_channels=True, flip_h=fh, flip_v=fv)
+            stack, = self.augment([stack], res, seed)
+        else:
+            sharp, blur, stack = self.augment([prepared["sharp"].to(dev), prepared["blur"].to(dev), stack], res, seed)
+        if "noise" in prepared:
+            stack = (stack[None] + prepared["noise"].to(dev))[0]
+        return self.assemble(sharp, blur, stack, prepared["duty"])
+
+    def __getitem__(self, index, seed=None):
+        return self.finish(self.prepare(index, seed))
 
 
 class RealBlurClipDataset:
@@ -426,12 +515,45 @@ def collate(samples):
     return {k: torch.stack([s[k] for s in samples]) for k in samples[0]}
 
 
-def batches(dataset, batch_size, rank=0, world=1, seed=0, epochs=None, shuffle=True, drop_last=True):
-    """Per-rank batches: a seeded permutation per epoch split round-robin over ranks (what DistributedSampler does,
-    h5dataloader.py:47-57); yields collated dicts [B, L=1, ...]."""
+def _prefetched(dataset, plan, depth):
+    """Batches of `plan` (an iterator of [(index, item seed), ...] lists) with the host half of up to `depth` batches made
+    ahead by ONE worker thread (`dataset.prepare`); the calling thread runs `dataset.finish` and collates, so every GPU call
+    stays on the caller's thread and stream.  An exception in the worker is re-raised here at the batch it belongs to; closing
+    or exhausting the generator joins the worker."""
+    ready, slots, stop = queue.SimpleQueue(), threading.Semaphore(int(depth)), threading.Event()
+
+    def work():
+        try:
+            for idx in plan:
+                slots.acquire()               # one slot per batch in flight, released when the consumer takes the batch
+                if stop.is_set():
+                    return
+                ready.put(([dataset.prepare(i, seed) for i, seed in idx], None))
+            ready.put((None, None))
+        except BaseException as e:            # (handed over: the consumer raises it after the batches made before it)
+            ready.put((None, e))
+
+    worker = threading.Thread(target=work, name="clipdata-prefetch", daemon=True)
+    worker.start()
+    try:
+        while True:
+            prepared, err = ready.get()
+            if err is not None:
+                raise err
+            if prepared is None:
+                return
+            slots.release()
+            yield collate([dataset.finish(p) for p in prepared])
+    finally:
+        stop.set()
+        slots.release()
+        worker.join()
+
+
+def _train_plan(n, batch_size, rank, world, seed, epochs, shuffle, drop_last):
     epoch = 0
     while epochs is None or epoch < epochs:
-        order = list(range(len(dataset)))
+        order = list(range(n))
         if shuffle:
             random.Random(seed + epoch).shuffle(order)
         order = order[rank::world]
@@ -439,8 +561,21 @@ def batches(dataset, batch_size, rank=0, world=1, seed=0, epochs=None, shuffle=T
             idx = order[k:k + batch_size]
             if len(idx) < batch_size and drop_last:
                 break
-            yield collate([dataset.__getitem__(i, seed=seed + 7919 * epoch + i) for i in idx])
+            yield [(i, seed + 7919 * epoch + i) for i in idx]
         epoch += 1
+
+
+def batches(dataset, batch_size, rank=0, world=1, seed=0, epochs=None, shuffle=True, drop_last=True, prefetch=0):
+    """Per-rank batches: a seeded permutation per epoch split round-robin over ranks (what DistributedSampler does,
+    h5dataloader.py:47-57); yields collated dicts [B, L=1, ...].  prefetch = k >= 1: the host half of up to k batches is made
+    ahead on a worker thread (`_prefetched`; the dataset needs `prepare` / `finish`); 0: everything on this thread, through
+    `dataset.__getitem__`.  The batches are the same either way."""
+    plan = _train_plan(len(dataset), batch_size, rank, world, seed, epochs, shuffle, drop_last)
+    if prefetch:
+        yield from _prefetched(dataset, plan, prefetch)
+        return
+    for idx in plan:
+        yield collate([dataset.__getitem__(i, seed=s) for i, s in idx])
 
 
 def shard_indices(n, rank, world):
@@ -457,16 +592,18 @@ def shard_indices(n, rank, world):
     return [(rank + k * world) % n for k in range(per)]
 
 
-def eval_batches(dataset, batch_size, rank=0, world=1, seed=0, drop_last=False):
+def eval_batches(dataset, batch_size, rank=0, world=1, seed=0, drop_last=False, prefetch=0):
     """One pass over `dataset` in file order for validation (the reference's valid_dataloader: no shuffle, DistributedSampler
     shards, h5dataloader.py:47-57): this rank's `shard_indices` in batches of `batch_size`; yields collated dicts [B, L=1, ...].
-    The item seeds depend on the index only, so every pass produces the same tensors."""
+    The item seeds depend on the index only, so every pass produces the same tensors.  prefetch: as for `batches`."""
     order = shard_indices(len(dataset), rank, world)
-    for k in range(0, len(order), batch_size):
-        idx = order[k:k + batch_size]
-        if len(idx) < batch_size and drop_last:
-            break
-        yield collate([dataset.__getitem__(i, seed=seed + i) for i in idx])
+    plan = ([(i, seed + i) for i in order[k:k + batch_size]] for k in range(0, len(order), batch_size)
+            if not (len(order) - k < batch_size and drop_last))
+    if prefetch:
+        yield from _prefetched(dataset, plan, prefetch)
+        return
+    for idx in plan:
+        yield collate([dataset.__getitem__(i, seed=s) for i, s in idx])
 
 
 def model_inputs(batch):

@@ -10,6 +10,10 @@ crosses the bus at one byte per sample.
 NaN; NaN gives 0, where numpy's cast is undefined.  A load's restored frames come back at one byte per sample, already in the
 layout an image writer takes.
 
+``period_to_planar``: the training reader's form of the first (ClipDataset(frames="device")): the n stored frames of a period
+-> (sharp [n, 3, h, w], blur [3, h, w]) in one pass, sharp as ``frames_to_planar`` writes it and blur bit-identical to
+``torch.from_numpy(frames[:e].mean(0)).permute(2, 0, 1).float() / 255`` (dataloader/h5dataset.py:311).
+
 Inputs must be GPU tensors; there is no CPU path.
 """
 import ctypes
@@ -41,6 +45,38 @@ def frames_to_planar(frames, window=None, reverse_channels=False, flip_h=False, 
                                               N.stream_ptr(frames.device))
     N.check(rc, "ebfi_frames_u8_to_planar")
     return out
+
+
+def _planar_out(name, out, shape, device):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise ValueError("period_to_planar: %s must be a contiguous float32 tensor of shape %r on %s" % (name, tuple(shape), device))
+    return out
+
+
+@torch.no_grad()
+def period_to_planar(frames, num_blur, window=None, reverse_channels=False, flip_h=False, flip_v=False, sharp_out=None,
+                     blur_out=None):
+    """frames: the n stored frames of one period, uint8 [n, H0, W0, 3] on the GPU, as `frames_to_planar` takes them.  Returns
+    (sharp float32 [n, 3, h, w], blur float32 [3, h, w]): sharp is `frames_to_planar` of the same arguments, blur the mean of
+    the first `num_blur` frames.  sharp_out / blur_out: contiguous destinations to fill (slices of a batch tensor), allocated
+    otherwise."""
+    N.require_gpu(frames, sharp_out, blur_out)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("period_to_planar: expected uint8 [n, H, W, 3], got %s %r" % (frames.dtype, tuple(frames.shape)))
+    if frames.stride(3) != 1:
+        frames = frames.contiguous()
+    n, H0, W0 = (int(v) for v in frames.shape[:3])
+    i, j, h, w = (0, 0, H0, W0) if window is None else (int(v) for v in window)
+    sharp = _planar_out("sharp_out", sharp_out, (n, 3, max(h, 0), max(w, 0)), frames.device)
+    blur = _planar_out("blur_out", blur_out, (3, max(h, 0), max(w, 0)), frames.device)
+    with torch.cuda.device_of(frames):
+        rc = N.lib().ebfi_period_frames_u8(N.ptr(frames), _i64x3(frames.stride()[:3]), n, int(num_blur), H0, W0, i, j, h, w,
+                                           int(bool(reverse_channels)), int(bool(flip_h)), int(bool(flip_v)), N.ptr(sharp),
+                                           N.ptr(blur), N.stream_ptr(frames.device))
+    N.check(rc, "ebfi_period_frames_u8")
+    return sharp, blur
 
 
 @torch.no_grad()

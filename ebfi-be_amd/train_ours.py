@@ -206,7 +206,18 @@ def resume_checkpoint(path, eng, scheduler, config, reset=False, map_location="c
     return start
 
 
-def real_data_passes(path, config, B, TB, device, rank, world, seed):
+def add_loader_arguments(ap):
+    """--loader / --prefetch of the recorded-clip readers (train_ours.py and train_ours_exposuredecision.py)."""
+    ap.add_argument("--loader", default="device", choices=["device", "host"],
+                    help="recorded clips: 'device' uploads the crop window's rows as uint8 and makes the sharp planes and the "
+                         "blurry mean in one kernel; 'host' converts and averages whole frames on the host.  The tensors are "
+                         "bit-identical")
+    ap.add_argument("--prefetch", type=int, default=1,
+                    help="recorded clips: batches whose host half (file reads, staging, noise draw) a worker thread prepares "
+                         "ahead while the current batch trains; 0 = everything synchronously in the training loop")
+
+
+def real_data_passes(path, config, B, TB, device, rank, world, seed, loader="device", prefetch=1):
     """Endless stream of (Frame, Event, T, GTEx, LatentF) passes from recorded clips (ebfi_amd.clipdata): the dataset keys
     are the reference's (config train_dataloader.dataset, train_ours.yml:115-150); defaults = its shipped values."""
     from ebfi_amd import clipdata
@@ -216,10 +227,10 @@ def real_data_passes(path, config, B, TB, device, rank, world, seed):
                               frames_per_blurry=int(ds_cfg.get("NumFramePerBlurry", 16)),
                               exposure_method=ds_cfg.get("ExposureMethod", "Custom"),
                               exposure_time=ds_cfg.get("ExposureTime", [9, 10, 11, 12, 13, 14, 15]),
-                              device=device, seed=seed, **clipdata.dataset_args_from_config(ds_cfg))
+                              device=device, seed=seed, frames=loader, **clipdata.dataset_args_from_config(ds_cfg))
     if len(ds) < B * world:
         raise SystemExit("--data: %d periods in %s, need at least batch_size x world = %d" % (len(ds), path, B * world))
-    for batch in clipdata.batches(ds, B, rank=rank, world=world, seed=seed):
+    for batch in clipdata.batches(ds, B, rank=rank, world=world, seed=seed, prefetch=prefetch):
         for inputs in clipdata.model_inputs(batch):
             yield inputs
 
@@ -238,10 +249,11 @@ def validation_batches(vs, config, args, B, H, W, TB, device, rank, world):
                                   frames_per_blurry=int(ds_cfg.get("NumFramePerBlurry", 16)),
                                   exposure_method=ds_cfg.get("ExposureMethod", "Custom"),
                                   exposure_time=ds_cfg.get("ExposureTime", [9, 10, 11, 12, 13, 14, 15]),
-                                  device=device, seed=args.seed, **clipdata.dataset_args_from_config(ds_cfg))
+                                  device=device, seed=args.seed, frames=args.loader, **clipdata.dataset_args_from_config(ds_cfg))
         if len(ds) == 0:
             raise SystemExit("--valid-data: no complete period in %s" % vs["valid_data"])
-        return lambda: clipdata.eval_batches(ds, vb, rank=rank, world=world, seed=args.seed, drop_last=vs["drop_last"])
+        return lambda: clipdata.eval_batches(ds, vb, rank=rank, world=world, seed=args.seed, drop_last=vs["drop_last"],
+                                             prefetch=args.prefetch)
     seeds = validation_seeds(args.seed, vs["valid_batches"])
     num_f = int(ds_cfg.get("NumFramePerPeriod", 4))
     mine = [synthetic_validation_batch(vb, H, W, TB, num_f, device=device, seed=seeds[j])
@@ -296,6 +308,7 @@ def main():
     ap.add_argument("--raw-events", action="store_true",
                     help="build the event tensor from synthetic raw event lists with the device events_to_stack kernel "
                          "(the reference's data path, h5dataset.py:327-352) instead of drawing voxel counts directly")
+    add_loader_arguments(ap)
     args = ap.parse_args()
     with open(args.config) as fh:
         config = yaml.safe_load(fh)
@@ -327,7 +340,7 @@ def main():
     # capture: Engine.settled): what is logged is the steady-state rate, whole job (all ranks)
     t0, frames, it = None, 0, start
     make = synthetic_batch_from_raw_events if args.raw_events else synthetic_batch
-    real = real_data_passes(args.data, config, B, TB, device, rank, world, args.seed) if args.data else None
+    real = real_data_passes(args.data, config, B, TB, device, rank, world, args.seed, args.loader, args.prefetch) if args.data else None
     valid_stamp, valid_batches, tracker = 1, None, None
     if vs["do_validation"]:
         from ebfi_amd.metrics import MetricTracker
@@ -385,6 +398,8 @@ def main():
         if scheduler is not None and it % st["lr_change_rate"] == 0 and it != 0 and lr_now >= st["lr_min"]:   # :335-338
             scheduler.step()
         it += 1
+    if real is not None:
+        real.close()                     # (joins the loader's worker thread)
     if rank == 0 and eng.book is not None:
         # fp16 backward (ebfi_amd.f16scale): optimiser steps skipped because an operand left the fp16 range (expected: 0)
         print("fp16 backward: %d of %d optimiser steps skipped by the overflow guard, %d operand scale slots"

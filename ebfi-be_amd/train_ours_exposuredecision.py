@@ -29,8 +29,8 @@ import yaml
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
-from train_ours import (CHECKPOINT_KEYS, TRAINING_MODE, Monitor, best_checkpoint_name, build_lr_scheduler,  # noqa: E402,F401
-                        checkpoint_state, init_distributed_mode, resume_checkpoint, run_validation, save_checkpoint,
+from train_ours import (CHECKPOINT_KEYS, TRAINING_MODE, Monitor, add_loader_arguments, best_checkpoint_name,  # noqa: E402,F401
+                        build_lr_scheduler, checkpoint_state, init_distributed_mode, resume_checkpoint, run_validation, save_checkpoint,
                         trainer_settings, validation_seeds, validation_settings)
 from ebfi_amd.dp import reduce_tensor  # noqa: E402
 from ebfi_amd.exposure_engine import (BLURRY_FASHIONS, check_fashion, check_model_name,  # noqa: E402,F401
@@ -65,6 +65,7 @@ def build_parser():
     ap.add_argument("--valid-data", default=None,
                     help="validation clips instead of valid_dataloader.path_to_datalist_txt (with trainer.do_validation; without "
                          "either: a fixed set of trainer.valid_batches synthetic batches)")
+    add_loader_arguments(ap)
     return ap
 
 
@@ -87,17 +88,17 @@ def exposure_settings(config):
             "height": int(tr.get("height", 128)), "width": int(tr.get("width", 128))}
 
 
-def _clip_dataset(path, ds_cfg, es, device, seed):
+def _clip_dataset(path, ds_cfg, es, device, seed, loader):
     from ebfi_amd import clipdata
     return clipdata.ClipDataset(path, time_bins=int(ds_cfg.get("time_bins", es["TB"])),
                                 frames_per_period=int(ds_cfg.get("NumFramePerPeriod", 16)),
                                 frames_per_blurry=int(ds_cfg.get("NumFramePerBlurry", 16)),
                                 exposure_method=ds_cfg.get("ExposureMethod", "Custom"),
                                 exposure_time=ds_cfg.get("ExposureTime", DEFAULT_EXPOSURE_TIME),
-                                device=device, seed=seed, **clipdata.dataset_args_from_config(ds_cfg))
+                                device=device, seed=seed, frames=loader, **clipdata.dataset_args_from_config(ds_cfg))
 
 
-def real_data_periods(path, config, es, device, rank, world, seed):
+def real_data_periods(path, config, es, device, rank, world, seed, loader="device", prefetch=1):
     """Endless stream of (Frame [B,3,H,W], Event [B,TB,2,H,W], Duty [B,1]) micro-steps from recorded clips: one per period of
     every load of a collated batch, in the reference's order (:221-231)."""
     from ebfi_amd import clipdata
@@ -105,7 +106,7 @@ def real_data_periods(path, config, es, device, rank, world, seed):
     B = es["batch_size"]
     if len(ds) < B * world:
         raise SystemExit("--data: %d periods in %s, need at least batch_size x world = %d" % (len(ds), path, B * world))
-    for batch in clipdata.batches(ds, B, rank=rank, world=world, seed=seed):
+    for batch in clipdata.batches(ds, B, rank=rank, world=world, seed=seed, prefetch=prefetch):
         frames, events, duties = batch["SeqBlurryF"], batch["SeqHREv"], batch["SeqExposureDuty"]
         for load in range(frames.shape[1]):
             for i in range(frames.shape[2]):
@@ -118,10 +119,11 @@ def validation_batches(vs, es, args, device, rank, world):
     from ebfi_amd import clipdata
     vb = vs["batch_size"] or es["batch_size"]
     if vs["valid_data"]:
-        ds = _clip_dataset(vs["valid_data"], vs["dataset"], es, device, args.seed)
+        ds = _clip_dataset(vs["valid_data"], vs["dataset"], es, device, args.seed, args.loader)
         if len(ds) == 0:
             raise SystemExit("--valid-data: no complete period in %s" % vs["valid_data"])
-        return lambda: clipdata.eval_batches(ds, vb, rank=rank, world=world, seed=args.seed, drop_last=vs["drop_last"])
+        return lambda: clipdata.eval_batches(ds, vb, rank=rank, world=world, seed=args.seed, drop_last=vs["drop_last"],
+                                             prefetch=args.prefetch)
     seeds = validation_seeds(args.seed, vs["valid_batches"])
     mine = [synthetic_exposure_batch(vb, es["height"], es["width"], es["TB"], es["exposure_time"], es["frames_per_period"],
                                      device=device, seed=seeds[j]) for j in clipdata.shard_indices(len(seeds), rank, world)]
@@ -157,7 +159,7 @@ def main(argv=None):
     runid = args.runid or str(config.get("id") or "run")
     out_dir = os.path.join(tr.get("output_path", "./output"), "models", config.get("experiment", "ExposurePretrain"), runid)
 
-    real = real_data_periods(args.data, config, es, device, rank, world, args.seed) if args.data else None
+    real = real_data_periods(args.data, config, es, device, rank, world, args.seed, args.loader, args.prefetch) if args.data else None
     valid_stamp, valid_batches, tracker = 1, None, None
     if vs["do_validation"]:
         valid_batches = validation_batches(vs, es, args, device, rank, world)
@@ -210,6 +212,8 @@ def main(argv=None):
         if scheduler is not None and it % st["lr_change_rate"] == 0 and it != 0 and lr_now >= st["lr_min"]:   # :311-314
             scheduler.step()
         it += 1
+    if real is not None:
+        real.close()                     # (joins the loader's worker thread)
     if world > 1:
         dist.destroy_process_group()
 

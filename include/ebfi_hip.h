@@ -38,6 +38,7 @@
  *   ebfi_frame2lap / _frame2dcp myutils/utils.py:34-49 / :15-31
  *   ebfi_frames_u8_to_planar    GetFrames of the real-data reader (dataloader/h5dataset_realdata.py:178-189) + AugmentData's crop / flips
  *   ebfi_planar_to_u8           the uint8 image cast of the evaluation loop (infer_ours.py:135)
+ *   ebfi_period_frames_u8       GetFrames of the synthetic-blur reader (dataloader/h5dataset.py:296-311): sharp frames + exposure mean
  *   ebfi_event_cnt_image        event_visualisation.plot_event_cnt of the evaluation loop (infer_ours.py:139-142,
  *                               myutils/vis_events/matplotlib_plot_events.py:127-251)
  *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
@@ -86,7 +87,8 @@ extern "C" {
  *      pure addition under 14, ebfi_charbonnier_workspace / _forward / _backward (the validation loop's Charbonnier loss); and
  *      ebfi_duty_head_workspace / _forward / _backward (the duty head and MSE loss of the stage-1 pre-training), likewise; and
  *      ebfi_frames_u8_to_planar / ebfi_planar_to_u8 (the frame upload and download of an inference run on recorded clips); and
- *      ebfi_event_cnt_image_workspace / ebfi_event_cnt_image (the event-count images of the evaluation loop), likewise */
+ *      ebfi_event_cnt_image_workspace / ebfi_event_cnt_image (the event-count images of the evaluation loop), likewise; and
+ *      ebfi_period_frames_u8 (the sharp frames and the exposure mean of a training period from its stored bytes), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -743,6 +745,23 @@ int ebfi_duty_head_backward(const float *g, const float *Ex, const float *duty, 
 int ebfi_frames_u8_to_planar(const uint8_t *src, const int64_t src_strides[3], int64_t n, int H0, int W0, int i, int j, int h,
                              int w, int reverse_channels, int flip_h, int flip_v, float *out, void *stream);
 int ebfi_planar_to_u8(const float *in, const int64_t in_strides[3], int64_t n, int H, int W, uint8_t *out, void *stream);
+
+/* ebfi_period_frames_u8: one period of a TRAINING item (the synthetic-blur reader, dataloader/h5dataset.py:296-311) in one pass
+ * over its n stored frames.  Source layout, window, channel reversal and flips are those of ebfi_frames_u8_to_planar;
+ *   sharp float32 [n][3][h][w], contiguous: sharp[f] is what ebfi_frames_u8_to_planar writes for frame f;
+ *   blur  float32 [3][h][w], contiguous: the mean of the first n_blur frames of the same window,
+ *     blur[c][y][x] = (float) ((double) (sum over f < n_blur of the byte) / (double) n_blur) / 255.0f
+ * i.e. `torch.from_numpy(FNumpy[:n_blur].mean(0)).permute(2, 0, 1).float() / 255` (h5dataset.py:311), bit for bit: the byte sum
+ * is an exact integer, numpy's mean divides it in float64, the quotient is rounded to fp32 and divided by 255 in fp32 -- three
+ * roundings, made here in the same places (a fused sum / (255 * n_blur) gives other bits).  Every source byte is read once.
+ * `sharp` and `blur` may point into larger tensors (a slot of a batch): 16-byte stores are used when w % 4 == 0 and BOTH
+ * pointers are 16-byte aligned, 4-byte loads under the conditions of ebfi_frames_u8_to_planar, the scalar path otherwise.
+ * One thread owns four pixels of a row and walks the frames.  One launch on `stream`, no workspace, no host synchronisation.
+ * Null pointers, n < 1, n_blur < 1, n_blur > n (or > 2^24), sizes < 1, a window that leaves the frame, a negative stride (pixel
+ * stride < 3) -> EBFI_ERR_ARG before anything touches the GPU. */
+int ebfi_period_frames_u8(const uint8_t *src, const int64_t src_strides[3], int64_t n, int64_t n_blur, int H0, int W0, int i,
+                          int j, int h, int w, int reverse_channels, int flip_h, int flip_v, float *sharp, float *blur,
+                          void *stream);
 
 /* ------------------------------------------------------------------ event-count images of the evaluation loop
  * ebfi_event_cnt_image: n images of two polarity planes, float32 (value (f, p, y, x) at ev + f * ev_strides[0] + p * ev_strides[1]
