@@ -2234,6 +2234,34 @@ __global__ __launch_bounds__(256) void pack_table_bf16_kernel(const float *__res
     out[e] = (t >= 0 && (t & 0x40000000)) ? (__bf16)(v - (float)h) : h;
 }
 
+// The same images from ONE table entry and ONE gather per (hi, lo) pair: 12 bytes per pair (index, source, two bf16 stores) where
+// the table above costs 20.  `table` holds, per image, the source index of every element (negative: structural zero) padded to
+// whole blocks of PACK_PAIR_BLOCK entries; desc[blk] = {position of the block's first hi element in `out` (two 32-bit halves),
+// hi -> lo distance in elements (the image's size), valid entries of the block}.  Workgroup i packs block active[i]: the host
+// chooses which images a launch refreshes by listing their blocks (ebfi_amd/weightbank.py).  Images start on multiples of 16
+// elements and a thread takes two neighbouring entries, so every store is one aligned 32-bit word.
+constexpr int PACK_PAIR_BLOCK = 512;
+__global__ __launch_bounds__(256) void pack_pairs_bf16_kernel(const float *__restrict__ src, const int32_t *__restrict__ table,
+                                                              const int4 *__restrict__ desc, const int32_t *__restrict__ active,
+                                                              __bf16 *__restrict__ out) {
+    const int blk = active[blockIdx.x];
+    const int4 d = desc[blk];
+    const int e = 2 * threadIdx.x;
+    if (e >= d.w) return;
+    const int64_t hi_at = (int64_t)(((uint64_t)(uint32_t)d.y << 32) | (uint32_t)d.x) + e;
+    const int2 t = *reinterpret_cast<const int2 *>(table + (int64_t)blk * PACK_PAIR_BLOCK + e);
+    const float v0 = t.x >= 0 ? src[t.x] : 0.f, v1 = t.y >= 0 ? src[t.y] : 0.f;
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const __bf16 h0 = (__bf16)v0, h1 = (__bf16)v1;
+    bf16x2 hi, lo;
+    hi[0] = h0;
+    hi[1] = h1;
+    lo[0] = (__bf16)(v0 - (float)h0);
+    lo[1] = (__bf16)(v1 - (float)h1);
+    *reinterpret_cast<bf16x2 *>(out + hi_at) = hi;
+    *reinterpret_cast<bf16x2 *>(out + hi_at + d.z) = lo;
+}
+
 // 64 consecutive elements per workgroup, 4 thread rows each summing every 4th slab (4 loads in
 // flight), then a fixed-order combine through LDS: deterministic, and short dependent chains.
 // perm_cin > 0: the slabs hold the weight part as [co][tap][ci] (bf16 kernel); gw is always [co][ci][tap].
@@ -3363,6 +3391,23 @@ extern "C" int ebfi_pack_table_bf16(const float *src, const int32_t *table, int6
     hipLaunchKernelGGL(pack_table_bf16_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, src, table, n,
                        static_cast<__bf16 *>(out));
     return check_launch("pack_table_bf16");
+}
+
+extern "C" int ebfi_pack_pairs_block(void) { return PACK_PAIR_BLOCK; }
+
+// n_active blocks (ids in `active`) of the pair table; n_entries: the valid entries among them (the profiler's byte count)
+extern "C" int ebfi_pack_pairs_bf16(const float *src, const int32_t *table, const void *desc, const int32_t *active, int64_t n_active,
+                                    int64_t n_entries, void *out, void *stream) {
+    if (!src || !table || !desc || !active || !out || n_active < 0 || n_active > 2147483647LL || n_entries < 0 ||
+        n_entries > n_active * PACK_PAIR_BLOCK)
+        return fail(EBFI_ERR_ARG, "pack_pairs_bf16: bad argument");
+    if (n_active == 0) return EBFI_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // (the profiler's row keeps the name of the launch this one stands in for: the step's bf16 weight pack)
+    ProfScope ps("pack_table_bf16", st, 0.0, 12.0 * (double)n_entries + 20.0 * (double)n_active);
+    hipLaunchKernelGGL(pack_pairs_bf16_kernel, dim3((unsigned)n_active), dim3(256), 0, st, src, table, static_cast<const int4 *>(desc),
+                       active, static_cast<__bf16 *>(out));
+    return check_launch("pack_pairs_bf16");
 }
 
 extern "C" size_t ebfi_conv2d_packed_bytes(int Cin, int Cout, int ksize, int transposed) {

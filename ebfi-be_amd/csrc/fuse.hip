@@ -374,12 +374,18 @@ __global__ __launch_bounds__(256) void scalar_conv_fwd_kernel(ScalarBank bank, c
     }
 }
 
-// one workgroup for the whole bank (S*B*C values: 6144 for the default model): every sum in a fixed order
-__global__ __launch_bounds__(256) void scalar_conv_bwd_kernel(ScalarBank bank, const float *__restrict__ v, const float *__restrict__ out,
-                                                              const float *__restrict__ gout, float *__restrict__ gw, float *__restrict__ gb,
-                                                              float *__restrict__ gv, int S, int B, int K, int C, float slope) {
-    // grad_weight / grad_bias: thread = (layer, channel), walks the samples
-    for (int i = threadIdx.x; i < S * C; i += 256) {
+// The bank's backward over a grid of one-wave workgroups (before: one 256-thread workgroup walked all S*B*C = 6144 values of the
+// default model, ~23 us of back-to-back load latencies).  Workgroups [0, n_wb) take 64 (layer, channel) items each for
+// grad_weight / grad_bias; workgroup n_wb + p takes the (sample, input) pair p of grad_v.  Every sum keeps its order of additions:
+// the b walk per (layer, channel); the lane-strided (s, c) walk and the butterfly per pair.
+__global__ __launch_bounds__(64) void scalar_conv_bwd_kernel(ScalarBank bank, const float *__restrict__ v, const float *__restrict__ out,
+                                                             const float *__restrict__ gout, float *__restrict__ gw, float *__restrict__ gb,
+                                                             float *__restrict__ gv, int n_wb, int S, int B, int K, int C, float slope) {
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x < n_wb) {
+        // grad_weight / grad_bias: thread = (layer, channel), walks the samples
+        const int i = blockIdx.x * 64 + lane;
+        if (i >= S * C) return;
         const int s = i / C, c = i - s * C;
         float aw[SC_MAX_K], ab = 0.f;
 #pragma unroll
@@ -398,28 +404,27 @@ __global__ __launch_bounds__(256) void scalar_conv_bwd_kernel(ScalarBank bank, c
             for (int k = 0; k < SC_MAX_K; ++k)
                 if (k < K) gw[(int64_t)i * K + k] = aw[k];
         }
+        return;
     }
     // grad_v[b][k] = sum over (layer, channel): one wave per (b, k) pair, lanes stride the S*C terms, butterfly in fixed order
-    if (gv) {
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        for (int p = wave; p < B * K; p += 4) {
-            const int b = p / K, k = p - b * K;
-            float acc = 0.f;
-            for (int s = 0; s < S; ++s) {
-                const float *w = nullptr;
+    const int p = blockIdx.x - n_wb;
+    if (!gv || p >= B * K) return;
+    const int b = p / K, k = p - b * K;
+    float acc = 0.f;
+    for (int s = 0; s < S; ++s) {
+        // (constant-index walk over the by-value table, as in the forward)
+        const float *w = nullptr;
 #pragma unroll
-                for (int j = 0; j < SC_MAX_LAYERS; ++j)
-                    if (j == s) w = bank.w[j];
-                for (int c = lane; c < C; c += 64) {
-                    const int64_t o = ((int64_t)s * B + b) * C + c;
-                    acc = fmaf(gout[o] * (out[o] > 0.f ? 1.f : slope), w[c * K + k], acc);
-                }
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-            if (lane == 0) gv[p] = acc;
+        for (int j = 0; j < SC_MAX_LAYERS; ++j)
+            if (j == s) w = bank.w[j];
+        for (int c = lane; c < C; c += 64) {
+            const int64_t o = ((int64_t)s * B + b) * C + c;
+            acc = fmaf(gout[o] * (out[o] > 0.f ? 1.f : slope), w[c * K + k], acc);
         }
     }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if (lane == 0) gv[p] = acc;
 }
 }  // namespace
 
@@ -676,8 +681,10 @@ extern "C" int ebfi_scalar_conv_backward(const float *v, const void *const *weig
     hipStream_t st = static_cast<hipStream_t>(stream);
     {
         ProfScope ps("scalar_conv_bwd", st, 4.0 * S * B * C * K, 4.0 * (2.0 * S * B * C + 2.0 * S * C * (K + 1) + 2.0 * B * K));
-        hipLaunchKernelGGL(scalar_conv_bwd_kernel, dim3(1), dim3(256), 0, st, bank, v, out, grad_out, grad_weight, grad_bias, grad_v,
-                           S, B, K, C, slope);
+        const int n_wb = (grad_weight || grad_bias) ? (int)ceil_div(S * C, 64) : 0, n_v = grad_v ? B * K : 0;
+        if (n_wb + n_v > 0)
+            hipLaunchKernelGGL(scalar_conv_bwd_kernel, dim3((unsigned)(n_wb + n_v)), dim3(64), 0, st, bank, v, out, grad_out, grad_weight,
+                               grad_bias, grad_v, n_wb, S, B, K, C, slope);
     }
     return check_launch("scalar_conv_bwd");
 }

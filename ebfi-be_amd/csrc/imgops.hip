@@ -181,6 +181,175 @@ __global__ __launch_bounds__(CT *CT) void census_bwd_kernel(const float *__restr
     for (int c = 0; c < C; ++c) grad_x[((int64_t)b * C + c) * hw + (int64_t)py * W + px] = g;
 }
 
+// ---- two predictions against one target (the training loss: Sharp and Sharp_pre) --------------------------------------------
+// The single-pair kernels above are paced by VALU issue, not by memory: ~45 instructions per tap and pixel (two rsqrt with
+// their denormal-range guards, one IEEE division), 49 taps, a wave64 instruction every 4 cycles.  The pair kernels stage the
+// target's gray tile once, evaluate the target's census_t once per tap for both predictions, and take the reciprocal square
+// root straight from the hardware instruction: its argument is >= 0.81, never in the denormal range the guard of rsqrtf()
+// rescales, so the bits are those of rsqrtf().  Per prediction every expression, the tap order and the per-tile sums are
+// those of census_fwd_kernel / census_bwd_kernel as compiled (the contractions the compiler chose there are written out
+// here), so partial sums and gradients are bit-identical to the single-pair entry points.
+__device__ __forceinline__ float census_rsq(float s) { return __builtin_amdgcn_rsqf(s); }
+
+template <bool TWO>
+__device__ __forceinline__ void census_stage3(const float *__restrict__ xa, const float *__restrict__ xb, const float *__restrict__ y,
+                                              int C, int H, int W, int b, int ty0, int tx0, float (*ga)[CTW + 1],
+                                              float (*gb)[CTW + 1], float (*gy)[CTW + 1]) {
+    const int64_t hw = (int64_t)H * W;
+    const float invc = 1.f / (float)C;
+    for (int i = threadIdx.x; i < CTW * CTW; i += CT * CT) {
+        const int ly = i / CTW, lx = i - ly * CTW;
+        const int py = ty0 + ly - CR, px = tx0 + lx - CR;
+        float sa = 0.f, sb = 0.f, sy = 0.f;
+        if (py >= 0 && py < H && px >= 0 && px < W) {
+            const int64_t o = (int64_t)b * C * hw + (int64_t)py * W + px;
+            if (C == 3) {   // (the images of the loss: every load in flight before the first add; the same order of additions)
+                const float a0 = xa[o], a1 = xa[o + hw], a2 = xa[o + 2 * hw];
+                const float y0 = y[o], y1 = y[o + hw], y2 = y[o + 2 * hw];
+                float b0 = 0.f, b1 = 0.f, b2 = 0.f;
+                if (TWO) { b0 = xb[o]; b1 = xb[o + hw]; b2 = xb[o + 2 * hw]; }
+                sa = ((sa + a0) + a1) + a2;
+                sy = ((sy + y0) + y1) + y2;
+                sb = ((sb + b0) + b1) + b2;
+            } else {
+                for (int c = 0; c < C; ++c) {
+                    sa += xa[o + c * hw];
+                    sy += y[o + c * hw];
+                    if (TWO) sb += xb[o + c * hw];
+                }
+            }
+            sa *= invc;
+            sb *= invc;
+            sy *= invc;
+        }
+        ga[ly][lx] = sa;
+        gy[ly][lx] = sy;
+        if (TWO) gb[ly][lx] = sb;
+    }
+}
+
+// one (pixel, tap) term of the forward given the prediction's difference and the target's census_t
+__device__ __forceinline__ float census_fterm(float dx, float ty) {
+    const float u = fmaf(dx, census_rsq(fmaf(dx, dx, 0.81f)), -ty);
+    return __fdiv_rn(__fmul_rn(u, u), fmaf(u, u, 0.1f));
+}
+
+__device__ __forceinline__ void census_tile_sum(float acc, float *red, float *dst) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) *dst = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// partial[0 .. P) of xa, partial[P .. 2P) of xb (P = ebfi_census_partials), each as census_fwd_kernel writes it
+template <bool TWO>
+__global__ __launch_bounds__(CT *CT) void census2_fwd_kernel(const float *__restrict__ xa, const float *__restrict__ xb,
+                                                             const float *__restrict__ y, float *__restrict__ partial, int64_t P,
+                                                             int C, int H, int W) {
+    __shared__ float ga[CTW][CTW + 1], gb[TWO ? CTW : 1][CTW + 1], gy[CTW][CTW + 1];
+    __shared__ float red[2][4];
+    const int b = blockIdx.z, ty0 = blockIdx.y * CT, tx0 = blockIdx.x * CT;
+    census_stage3<TWO>(xa, xb, y, C, H, W, b, ty0, tx0, ga, gb, gy);
+    __syncthreads();
+    const int ly = threadIdx.x / CT, lx = threadIdx.x % CT;
+    const int py = ty0 + ly, px = tx0 + lx;
+    float acca = 0.f, accb = 0.f;
+    if (py >= CR && py < H - CR && px >= CR && px < W - CR) {
+        const float ca = ga[ly + CR][lx + CR], cy = gy[ly + CR][lx + CR], cb = TWO ? gb[ly + CR][lx + CR] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 7; ++i)
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {
+                const float dy = gy[ly + i][lx + j] - cy;
+                const float ty = __fmul_rn(dy, census_rsq(fmaf(dy, dy, 0.81f)));
+                acca += census_fterm(ga[ly + i][lx + j] - ca, ty);
+                if (TWO) accb += census_fterm(gb[ly + i][lx + j] - cb, ty);
+            }
+        acca *= (1.f / 49.f);
+        accb *= (1.f / 49.f);
+    }
+    const int64_t tile = ((int64_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    census_tile_sum(acca, red[0], partial + tile);
+    if (TWO) census_tile_sum(accb, red[1], partial + P + tile);
+}
+
+// loss[0] = wa * sum(partial[0..P)) / n (+ wb * sum(partial[P..2P)) / n): one workgroup, every sum in a fixed order
+template <bool TWO>
+__global__ __launch_bounds__(256) void census2_finish_kernel(const float *__restrict__ partial, int64_t P, float n, float wa, float wb,
+                                                             float *__restrict__ loss) {
+    __shared__ float red[2][4];
+    float sa = 0.f, sb = 0.f;
+    for (int64_t i = threadIdx.x; i < P; i += 256) {
+        sa += partial[i];
+        if (TWO) sb += partial[P + i];
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        sa += __shfl_xor(sa, d, 64);
+        if (TWO) sb += __shfl_xor(sb, d, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = sa;
+        red[1][threadIdx.x >> 6] = sb;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float la = __fmul_rn(wa, __fdiv_rn((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), n));
+        const float lb = __fmul_rn(wb, __fdiv_rn((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]), n));
+        loss[0] = TWO ? la + lb : la;
+    }
+}
+
+// dL/dd of one (pixel, tap) term given the prediction's difference and the target's census_t: census_dterm as compiled
+__device__ __forceinline__ float census_dterm_t(float dx, float ty) {
+    const float rx = census_rsq(fmaf(dx, dx, 0.81f));
+    const float u = fmaf(dx, rx, -ty);
+    const float den = fmaf(u, u, 0.1f);
+    return __fmul_rn(__fdiv_rn(__fmul_rn(0.2f, u), __fmul_rn(den, den)), __fmul_rn(__fmul_rn(__fmul_rn(0.81f, rx), rx), rx));
+}
+
+// grad_xa = wa * grad[0] * d census(xa, y) / d xa, grad_xb likewise with wb: census_bwd_kernel per prediction
+template <bool TWO>
+__global__ __launch_bounds__(CT *CT) void census2_bwd_kernel(const float *__restrict__ xa, const float *__restrict__ xb,
+                                                             const float *__restrict__ y, const float *__restrict__ grad_loss,
+                                                             float wa, float wb, float *__restrict__ grad_xa,
+                                                             float *__restrict__ grad_xb, int C, int H, int W, float norm) {
+    __shared__ float ga[CTW][CTW + 1], gb[TWO ? CTW : 1][CTW + 1], gy[CTW][CTW + 1];
+    const int b = blockIdx.z, ty0 = blockIdx.y * CT, tx0 = blockIdx.x * CT;
+    census_stage3<TWO>(xa, xb, y, C, H, W, b, ty0, tx0, ga, gb, gy);
+    __syncthreads();
+    const int ly = threadIdx.x / CT, lx = threadIdx.x % CT;
+    const int py = ty0 + ly, px = tx0 + lx;
+    if (py >= H || px >= W) return;
+    const float ca = ga[ly + CR][lx + CR], cy = gy[ly + CR][lx + CR], cb = TWO ? gb[ly + CR][lx + CR] : 0.f;
+    const float self_in = (py >= CR && py < H - CR && px >= CR && px < W - CR) ? 1.f : 0.f;
+    float acca = 0.f, accb = 0.f;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        const int qy = py + (i - CR);
+        const bool row_in = qy >= CR && qy < H - CR;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const int qx = px + (j - CR);
+            const float wgt = self_in + ((row_in && qx >= CR && qx < W - CR) ? 1.f : 0.f);
+            const float dy = gy[ly + i][lx + j] - cy;
+            const float ty = __fmul_rn(dy, census_rsq(fmaf(dy, dy, 0.81f)));
+            acca = fmaf(-wgt, census_dterm_t(ga[ly + i][lx + j] - ca, ty), acca);
+            if (TWO) accb = fmaf(-wgt, census_dterm_t(gb[ly + i][lx + j] - cb, ty), accb);
+        }
+    }
+    const float gl = grad_loss[0];
+    const float g_a = __fdiv_rn(__fmul_rn(__fmul_rn(acca, norm), __fmul_rn(gl, wa)), (float)C);
+    const float g_b = __fdiv_rn(__fmul_rn(__fmul_rn(accb, norm), __fmul_rn(gl, wb)), (float)C);
+    const int64_t hw = (int64_t)H * W;
+    for (int c = 0; c < C; ++c) {
+        const int64_t o = ((int64_t)b * C + c) * hw + (int64_t)py * W + px;
+        grad_xa[o] = g_a;
+        if (TWO) grad_xb[o] = g_b;
+    }
+}
+
 // Adjoints of nn.ReflectionPad2d(p) (the detail branch's output conv, model_singleframe.py:207: ReflectionPad2d(3) before the
 // 7x7 convolution) and nn.ReplicationPad2d(p) (the FAC module, KernelConv2D.py:82-86): grad_in[i][j] = sum of the padded
 // gradient over the padded positions that map onto (i, j).  One thread per output pixel, a GATHER in a fixed order:
@@ -300,4 +469,63 @@ extern "C" int ebfi_census_backward(const float *x, const float *y, const float 
                            grad_x, C, H, W, norm);
     }
     return check_launch("census_bwd");
+}
+
+static int census_pair_check(const char *who, const void *xa, const void *y, int B, int C, int H, int W) {
+    if (!xa || !y) return fail(EBFI_ERR_ARG, "%s: null argument", who);
+    if (B < 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535) return fail(EBFI_ERR_ARG, "%s: bad dimensions", who);
+    return EBFI_OK;
+}
+
+// The two census terms of the training loss in one launch pair: partial[2 * ebfi_census_partials(B,H,W)] gets the per-tile sums of
+// (xa, y) then of (xb, y), each exactly as ebfi_census_forward writes them, and
+//   loss[0] = wa * sum(partial of xa) / (B*H*W) + wb * sum(partial of xb) / (B*H*W)
+// from a second, one-workgroup launch that adds the partials in a fixed order.  xb == NULL: one prediction, loss[0] = wa * (...).
+extern "C" int ebfi_census_pair_forward(const float *xa, const float *xb, const float *y, float wa, float wb, float *partial,
+                                        float *loss, int B, int C, int H, int W, void *stream) {
+    if (int rc = census_pair_check("census_pair_forward", xa, y, B, C, H, W)) return rc;
+    if (!partial || !loss) return fail(EBFI_ERR_ARG, "census_pair_forward: null argument");
+    if (B == 0) return fail(EBFI_ERR_ARG, "census_pair_forward: empty batch");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t P = ebfi_census_partials(B, H, W);
+    const dim3 grid(ceil_div(W, CT), ceil_div(H, CT), B);
+    const float n = (float)((double)B * (double)H * (double)W);
+    {
+        ProfScope ps("census2_fwd", st, 0.0, 4.0 * (xb ? 3 : 2) * B * C * (double)H * W);
+        if (xb)
+            hipLaunchKernelGGL(census2_fwd_kernel<true>, grid, dim3(CT * CT), 0, st, xa, xb, y, partial, P, C, H, W);
+        else
+            hipLaunchKernelGGL(census2_fwd_kernel<false>, grid, dim3(CT * CT), 0, st, xa, xb, y, partial, P, C, H, W);
+    }
+    if (int rc = check_launch("census2_fwd")) return rc;
+    {
+        ProfScope ps("census2_finish", st, 0.0, 4.0 * (xb ? 2 : 1) * (double)P);
+        if (xb)
+            hipLaunchKernelGGL(census2_finish_kernel<true>, dim3(1), dim3(256), 0, st, partial, P, n, wa, wb, loss);
+        else
+            hipLaunchKernelGGL(census2_finish_kernel<false>, dim3(1), dim3(256), 0, st, partial, P, n, wa, wb, loss);
+    }
+    return check_launch("census2_finish");
+}
+
+// grad_xa = d (wa * census(xa, y)) / d xa * grad_loss[0], grad_xb likewise with wb (xb == NULL: grad_xb is not touched): each
+// bit-identical to ebfi_census_backward given the 1-element gradient grad_loss[0] * w
+extern "C" int ebfi_census_pair_backward(const float *xa, const float *xb, const float *y, float wa, float wb, const float *grad_loss,
+                                         float *grad_xa, float *grad_xb, int B, int C, int H, int W, void *stream) {
+    if (int rc = census_pair_check("census_pair_backward", xa, y, B, C, H, W)) return rc;
+    if (!grad_loss || !grad_xa || (xb && !grad_xb)) return fail(EBFI_ERR_ARG, "census_pair_backward: null argument");
+    if (B == 0) return EBFI_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const float norm = (float)(1.0 / (49.0 * (double)B * (double)H * (double)W));
+    const dim3 grid(ceil_div(W, CT), ceil_div(H, CT), B);
+    {
+        ProfScope ps("census2_bwd", st, 0.0, 4.0 * (xb ? 5 : 3) * B * C * (double)H * W);
+        if (xb)
+            hipLaunchKernelGGL(census2_bwd_kernel<true>, grid, dim3(CT * CT), 0, st, xa, xb, y, grad_loss, wa, wb, grad_xa, grad_xb, C, H,
+                               W, norm);
+        else
+            hipLaunchKernelGGL(census2_bwd_kernel<false>, grid, dim3(CT * CT), 0, st, xa, xb, y, grad_loss, wa, wb, grad_xa, grad_xb, C,
+                               H, W, norm);
+    }
+    return check_launch("census2_bwd");
 }

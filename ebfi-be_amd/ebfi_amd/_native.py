@@ -69,6 +69,8 @@ SIGNATURES = {
     "ebfi_conv2d_packed_bytes": (_sz, [_i, _i, _i, _i]),
     "ebfi_conv2d_pack_bf16x3": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "ebfi_pack_table_bf16": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "ebfi_pack_pairs_block": (_i, []),
+    "ebfi_pack_pairs_bf16": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "ebfi_f16_scales_finish": (_i, [_vp, _i, _vp, _vp]),
     "ebfi_pack_table_f16": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "ebfi_conv2d_packed_f16": (_i, [_vp, _vp, _sz, _vp, _vp] + [_i] * 8 + [_i, _c.c_float, _vp, _vp, _i, _c.c_float, _vp, _vp, _vp]),
@@ -120,6 +122,8 @@ SIGNATURES = {
     "ebfi_census_partials": (_i64, [_i, _i, _i]),
     "ebfi_census_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ebfi_census_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ebfi_census_pair_forward": (_i, [_vp, _vp, _vp, _c.c_float, _c.c_float, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ebfi_census_pair_backward": (_i, [_vp, _vp, _vp, _c.c_float, _c.c_float, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ebfi_gauss5_forward": (_i, [_vp, _vp, _i64, _i, _i, _c.c_float, _vp]),
     "ebfi_gauss5_backward": (_i, [_vp, _vp, _i64, _i, _i, _c.c_float, _vp]),
     "ebfi_ed_head_workspace": (_sz, [_i, _i, _i64]),

@@ -160,6 +160,9 @@ class Engine:
             from . import f16scale
             self.book = f16scale.ScaleBook(self.device)
             self.bank.attach_scale_book(self.book)
+            # most data gradients and the KernelConv forward read the fp16 images under the book: the per-step pack covers a bf16
+            # image only once a kernel has asked for it (ebfi_amd.weightbank, pack_on_demand)
+            self.bank.pack_on_demand = True
             self.book.forward_f16 = forward_f16
 
     @property
@@ -272,6 +275,10 @@ class Engine:
             # measured on this batch (restoring them could undo the just-in-time calibration of a slot first met here).
             guard = self._guard()
             saved = None if guard is None else guard.clone()
+            if self.bank is not None and not self._graphs:
+                # the bf16 images the steady state reads are those the warm-up passes below ask for, not what the calibration
+                # steps asked for on their way (a later shape's capture only adds to the set: earlier graphs replay its prefix)
+                self.bank.forget_requests()
             side = torch.cuda.Stream(self.device)          # warm-up off the default stream (allocator, lazy inits)
             side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(side):

@@ -68,6 +68,53 @@ class _Census(torch.autograd.Function):
         return gx, None
 
 
+class _CensusPair(torch.autograd.Function):
+    """coef_a * census(a, target) + coef_b * census(b, target) (b may be None) on the two-prediction kernels of csrc/imgops.hip:
+    the target's tile and its per-tap transform are formed once for both, and the fixed-order sum of the per-tile partials, the
+    mean and the weighting are one small launch instead of torch reductions and 0-dim arithmetic."""
+
+    @staticmethod
+    def forward(ctx, a, b, target, coef_a, coef_b):
+        a, target = a.contiguous(), target.contiguous()
+        b = b.contiguous() if b is not None else None
+        B, C, H, W = a.shape
+        lib = N.lib()
+        partial = torch.empty(2 * int(lib.ebfi_census_partials(B, H, W)), dtype=torch.float32, device=a.device)
+        loss = torch.empty((), dtype=torch.float32, device=a.device)
+        with torch.cuda.device_of(a):
+            rc = lib.ebfi_census_pair_forward(N.ptr(a), N.ptr(b) if b is not None else None, N.ptr(target), float(coef_a),
+                                              float(coef_b), N.ptr(partial), N.ptr(loss), B, C, H, W, N.stream_ptr(a.device))
+        N.check(rc, "ebfi_census_pair_forward")
+        ctx.save_for_backward(*((a, target) if b is None else (a, target, b)))
+        ctx.coefs = (float(coef_a), float(coef_b))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a, target = ctx.saved_tensors[:2]
+        b = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        B, C, H, W = a.shape
+        g = g.contiguous().float().reshape(1)
+        ga = torch.empty_like(a)
+        gb = torch.empty_like(b) if b is not None else None
+        with torch.cuda.device_of(a):
+            rc = N.lib().ebfi_census_pair_backward(N.ptr(a), N.ptr(b) if b is not None else None, N.ptr(target), ctx.coefs[0],
+                                                   ctx.coefs[1], N.ptr(g), N.ptr(ga), N.ptr(gb) if b is not None else None,
+                                                   B, C, H, W, N.stream_ptr(a.device))
+        N.check(rc, "ebfi_census_pair_backward")
+        return ga, gb, None, None, None
+
+
+def census_pair(a, b, target, coef_a, coef_b):
+    """coef_a * Ternary()(a, target) + coef_b * Ternary()(b, target) for fp32 device images (b None: the first term alone)."""
+    N.require_gpu(a, target)
+    if a.dim() != 4 or a.shape != target.shape or (b is not None and b.shape != a.shape) or min(a.shape[-2:]) <= 6:
+        raise ValueError("census_pair takes [B, C, H, W] images of one shape with H, W > 6, got %s" % (tuple(a.shape),))
+    if any(t is not None and t.dtype != torch.float32 for t in (a, b, target)) or target.requires_grad:
+        raise ValueError("census_pair takes float32 images and a target that needs no gradient")
+    return _CensusPair.apply(a, b, target, coef_a, coef_b)
+
+
 class _LapLoss(torch.autograd.Function):
     """coef_a * Lap(a, target) + coef_b * Lap(b, target) (restore.py:166-213) as ONE pyramid of the difference planes
     [a - target ; b - target] on csrc/laploss.hip: the pyramid is linear, so lap_i(x) - lap_i(y) = lap_i(x - y)."""
@@ -210,9 +257,7 @@ class TrainLoss(nn.Module):
             c_sharp, c_pre, sharp_pre = 1.0, 0.0, None
         if _LapLoss.usable(sharp, sharp_pre, target):
             # one difference pyramid for both Laplacian terms; the census kernels work on the images themselves
-            total = _LapLoss.apply(sharp, sharp_pre, target, c_sharp, c_pre) + c_sharp * self.census(sharp, target)
-            if sharp_pre is not None:
-                total = total + c_pre * self.census(sharp_pre, target)
+            total = _LapLoss.apply(sharp, sharp_pre, target, c_sharp, c_pre) + census_pair(sharp, sharp_pre, target, c_sharp, c_pre)
             return total / accu_step
         with torch.no_grad():     # the target side of both terms is the same: compute it once
             yp = self.Lap.lap(target)

@@ -3,14 +3,22 @@
 The split-precision conv kernels (csrc/conv2d.hip) read their weights as two bf16 images (hi = bf16(w), lo = bf16(w - hi))
 in the layouts [tap][Cout][Cin16] (forward) and [tap][Cin][Cout16] with flipped taps (data gradient).  Round 1 rebuilt
 those images inside every conv call: 186 packing launches of ~5 us per training step for weights that change once per
-optimiser step.  Here they are produced for all layers at once by `ebfi_pack_table_bf16`, a gather driven by an index table
-built once on the host: entry e names the source element (in the flat parameter buffer) of packed element e.  Because the
-table is arbitrary, it also carries the layouts that used to need extra launches of their own:
+optimiser step.  Here they are produced for all layers at once by `ebfi_pack_pairs_bf16`, a gather driven by an index table
+built once on the host: per image, entry e names the source element (in the flat parameter buffer) of the image's element e,
+and one gather writes both hi[e] and lo[e].  (`bank.table` is the same thing in the one-entry-per-packed-element form of
+`ebfi_pack_table_bf16`, lo entries flagged with LO_FLAG: derived on the host when asked for.)  Because the table is arbitrary,
+it also carries the layouts that used to need extra launches of their own:
 
   * the depth-2 Conv3d / ConvTranspose3d folds of the detail branch (ebfi_amd.fold3d) -- table = fold(ids),
   * biases repeated over the folded channels (one `ebfi_gather_sum` launch for all of them),
   * several convolutions reading the same input as ONE convolution over concatenated output channels
     (`register_concat`: ResidualControl's Conv3[i][0] | Conv4[i][0], reference model_singleframe.py:127-131).
+
+The table is cut into blocks, and a launch packs the blocks on the bank's `block_list`: every image of every site by default.
+A bank with `pack_on_demand` set (the Engine's training bank with a scale book, where most data gradients and the KernelConv
+forward read the fp16 images instead) lists an image only once `fwd_ptr()` / `tr_ptr()` asked for it: the first request packs
+the image at once and appends its blocks, so that no pointer to bytes that were never packed leaves the bank; inside a stream
+capture a first request raises WeightImageError (the eager steps before the capture are what settle the set).
 
 A bank reads the parameters from one flat fp32 buffer: `FlatAdam.flat` in training (no copy), its own concatenation
 for inference.  Ops find their images through `lookup(param, kind)` while a bank is active (`with bank.active():`); without
@@ -25,6 +33,11 @@ from . import _native as N
 
 _ACTIVE = None
 LO_FLAG = 1 << 30
+
+
+class WeightImageError(Exception):
+    """A bf16 image was first asked for at a point where it cannot be packed (inside a stream capture).  Not a RuntimeError on
+    purpose: the Engine treats a RuntimeError during capture as 'continue with eager launches'; this must stop the run."""
 
 
 def active_bank():
@@ -45,9 +58,11 @@ class Site:
                  "fwd16_off", "fwd16_bytes", "fwd16_tag")
 
     def fwd_ptr(self):
+        self.bank._want(self, "fwd")
         return N._vp(self.bank.packed.data_ptr() + self.fwd_off)
 
     def tr_ptr(self):
+        self.bank._want(self, "tr")
         return N._vp(self.bank.packed.data_ptr() + self.tr_off)
 
     def tr16_ptr(self):
@@ -68,6 +83,9 @@ class Site:
     def bias(self):
         """fp32 [M] view of the (folded) bias inside the bank, or None."""
         return self.bank.bias_buf[self.bias_off:self.bias_off + self.M] if self.has_bias else None
+
+
+PAIR_BLOCK = 512     # entries per block of the pair table (csrc/conv2d.hip PACK_PAIR_BLOCK; checked against the library in _pack)
 
 
 def _ids_like(p, flat_off):
@@ -116,9 +134,18 @@ class WeightBank:
         if self.numel >= LO_FLAG:
             raise ValueError("more than 2^30 parameters")
         self.sites = {}
-        self._tables, self._n_packed = [], 0
+        # bf16 images: per image a piece of the pair table (source index per element, padded to whole blocks) and the blocks'
+        # descriptors [position of the first hi element (low, high word), hi -> lo distance, valid entries]
+        self._pair_tables, self._pair_desc, self._n_blocks, self._n_packed = [], [], 0, 0
+        self._images = {}              # (site key, "fwd" / "tr") -> (first block, blocks, elements)
         self._bias_tables, self._n_bias = [], 0
-        self.packed = self.table = self.bias_buf = self.bias_table = None
+        self.packed = self.bias_buf = self.bias_table = None
+        self._table = self.pair_table = self.pair_desc = self.block_list = None
+        # pack_on_demand: an image joins the per-step pack when fwd_ptr() / tr_ptr() first asks for it (see the module docstring);
+        # _wanted: those images in the order they were asked for; _n_active / _n_entries: the blocks listed, their valid entries
+        self.pack_on_demand = False
+        self._wanted, self._n_active, self._n_entries = [], 0, 0
+        self._wanted_set, self._retired = set(), []
         self._stamp = None
         # fp16 data-gradient images (ebfi_amd.f16scale / csrc/conv2d_f16.inc.hpp): built once a scale book is attached
         self.book = None
@@ -182,12 +209,20 @@ class WeightBank:
                 self._tables16.append(torch.cat([img.to(torch.int32), torch.full((padn,), -1, dtype=torch.int32)]))
                 self._segs.append((self._n16, s))
                 self._n16 += img.numel() + padn
+        PB = PAIR_BLOCK
         for name, img in (("fwd", fwd), ("tr", tr)) if need_tr else (("fwd", fwd),):
-            lo = torch.where(img >= 0, img | LO_FLAG, img)
+            n = img.numel()                      # (a multiple of 16: the kernel stores two neighbouring elements as one word)
+            assert n % 16 == 0
             setattr(s, name + "_off", 2 * self._n_packed)
-            setattr(s, name + "_bytes", 4 * img.numel())
-            self._tables += [img.to(torch.int32), lo.to(torch.int32)]
-            self._n_packed += 2 * img.numel()
+            setattr(s, name + "_bytes", 4 * n)
+            nb = (n + PB - 1) // PB
+            self._pair_tables.append(torch.cat([img.to(torch.int32), torch.full((nb * PB - n,), -1, dtype=torch.int32)]))
+            first = self._n_packed + PB * np.arange(nb, dtype=np.int64)
+            self._pair_desc.append(np.stack([first & 0xffffffff, first >> 32, np.full(nb, n, dtype=np.int64),
+                                             np.minimum(PB, n - PB * np.arange(nb, dtype=np.int64))], axis=1))
+            self._images[(key, name)] = (self._n_blocks, nb, n)
+            self._n_blocks += nb
+            self._n_packed += 2 * n
         # gradient routes back to the parameters (per source parameter: positions in the folded gradient)
         idn = ids.numpy()
         s.w_inv, s.w_R, s.w_shapes = [], [], [tuple(w.shape) for w in weights]
@@ -214,8 +249,30 @@ class WeightBank:
         self.packed = None            # (re)built at the next refresh
         return s
 
+    @property
+    def table(self):
+        """The bf16 images' table in the form `ebfi_pack_table_bf16` takes: one entry per packed element, [hi | lo] per image,
+        lo entries carrying LO_FLAG (a host tensor: the bank itself packs from the pair table)."""
+        if self._table is None and self._pair_tables:
+            parts = []
+            for (_, _, n), t in zip(self._images.values(), self._pair_tables):      # (both in registration order)
+                img = t[:n]
+                parts += [img, torch.where(img >= 0, img | LO_FLAG, img)]
+            self._table = torch.cat(parts)
+        return self._table
+
     def _finalize(self):
-        self.table = torch.cat(self._tables).to(self.device) if self._tables else None
+        self._table = None
+        if self._pair_tables:
+            self.pair_table = torch.cat(self._pair_tables).to(self.device)
+            self.pair_desc = torch.from_numpy(np.concatenate(self._pair_desc).astype(np.uint32).view(np.int32)).to(self.device)
+            # the blocks a pack launch covers: everything, or (pack_on_demand) the images asked for so far, in that order; room
+            # for all, so that a later request appends in place and a captured launch over the first n entries stays valid
+            self.block_list = torch.zeros(self._n_blocks, dtype=torch.int32, device=self.device)
+            listed = [self._images[k] for k in self._wanted] if self.pack_on_demand else list(self._images.values())
+            self._n_active = self._n_entries = 0
+            if listed:
+                self._list(np.concatenate([np.arange(first, first + nb) for first, nb, _ in listed]), sum(n for _, _, n in listed))
         self.packed = torch.empty(max(self._n_packed, 8), dtype=torch.bfloat16, device=self.device)
         self.bias_table = torch.cat(self._bias_tables).to(self.device) if self._bias_tables else None
         self.bias_buf = torch.empty(max(self._n_bias, 1), dtype=torch.float32, device=self.device)
@@ -228,6 +285,57 @@ class WeightBank:
                 counts.append((nxt - off) // 256)
             self.block_slot = torch.repeat_interleave(torch.tensor([site.w_slot for _, site in self._segs], dtype=torch.int32),
                                                       torch.tensor(counts)).to(self.device)
+
+    def _list(self, blocks, n):
+        """Append `blocks` (ids, holding n valid entries) to the active list."""
+        self.block_list[self._n_active:self._n_active + len(blocks)] = torch.from_numpy(np.asarray(blocks, dtype=np.int32))
+        self._n_active += len(blocks)
+        self._n_entries += n
+
+    def _pack(self, lib, st, start, n_blocks, n_entries):
+        """Launch over active[start : start + n_blocks]."""
+        if n_blocks:
+            if lib.ebfi_pack_pairs_block() != PAIR_BLOCK:
+                raise N.EbfiNativeError("the library packs blocks of %d entries, the bank's table has %d"
+                                        % (lib.ebfi_pack_pairs_block(), PAIR_BLOCK))
+            N.check(lib.ebfi_pack_pairs_bf16(N.ptr(self.flat), N.ptr(self.pair_table), N.ptr(self.pair_desc),
+                                             N._vp(self.block_list.data_ptr() + 4 * start), n_blocks, n_entries, N.ptr(self.packed), st),
+                    "ebfi_pack_pairs_bf16")
+
+    def _want(self, site, name):
+        """Called by Site.fwd_ptr() / tr_ptr(): under pack_on_demand, an image not yet in the per-step pack is packed now (from
+        the parameters the rest of the pack was made from) and listed for every later refresh."""
+        if not self.pack_on_demand or (site.key, name) in self._wanted_set:
+            return
+        if (site.key, name) not in self._images:
+            raise KeyError("site %r has no %s image" % (site.key, name))
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise WeightImageError("weight bank: the bf16 %s image of site %r is first asked for inside a stream capture; the eager "
+                                   "passes before the capture must run the same kernels as the captured one" % (name, site.key))
+        self._wanted.append((site.key, name))
+        self._wanted_set.add((site.key, name))
+        if self.packed is None:
+            self.refresh()                       # (finalises with the image listed and packs everything listed)
+            return
+        first, nb, n = self._images[(site.key, name)]
+        start = self._n_active
+        self._list(np.arange(first, first + nb), n)
+        with torch.cuda.device(self.device):
+            self._pack(N.lib(), N.stream_ptr(self.device), start, nb, n)
+
+    def packed_images(self):
+        """The (site key, "fwd" / "tr") images the per-step pack covers."""
+        return list(self._wanted) if self.pack_on_demand else list(self._images)
+
+    def forget_requests(self):
+        """pack_on_demand: start the set of requested images afresh (the Engine, before the eager passes that precede a capture:
+        the set then holds what the steady state reads, not what the calibration steps read on their way there).  A launch
+        captured earlier keeps the list it was captured with."""
+        if self.pack_on_demand and self._wanted:
+            self._wanted, self._wanted_set, self._n_active, self._n_entries = [], set(), 0, 0
+            if self.block_list is not None:
+                self._retired.append(self.block_list)
+                self.block_list = torch.zeros_like(self.block_list)
 
     def attach_scale_book(self, book):
         """Enable the fp16 data-gradient images: every 3x3 site gets a transposed fp16 image scaled by its own slot of `book`."""
@@ -250,9 +358,8 @@ class WeightBank:
         lib = N.lib()
         with torch.cuda.device(self.device):
             st = N.stream_ptr(self.device)
-            if self.table is not None:
-                N.check(lib.ebfi_pack_table_bf16(N.ptr(self.flat), N.ptr(self.table), self.table.numel(), N.ptr(self.packed), st),
-                        "ebfi_pack_table_bf16")
+            if self.pair_table is not None:
+                self._pack(lib, st, 0, self._n_active, self._n_entries)
             if self.bias_table is not None:
                 N.check(lib.ebfi_gather_sum(N.ptr(self.flat), N.ptr(self.bias_table), N.ptr(self.bias_buf), self._n_bias, 1, st),
                         "ebfi_gather_sum")

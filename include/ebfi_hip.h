@@ -249,6 +249,14 @@ size_t ebfi_conv2d_packed_bytes(int Cin, int Cout, int ksize, int transposed);
 int ebfi_conv2d_pack_bf16x3(const void *weight, int Cin, int Cout, int ksize, int transposed, void *packed,
                             size_t packed_bytes, void *stream);
 int ebfi_pack_table_bf16(const float *src, const int32_t *table, int64_t n, void *out, void *stream);
+/* The same [hi | lo] images from one table entry and one gather per (hi, lo) pair.  `table`: per image the source index of every
+ * element (negative: structural zero), padded to whole blocks of ebfi_pack_pairs_block() entries; `desc`: four int32 per block --
+ * the position in `out` (bf16 elements, low and high half of an int64) of the block's first hi element, the hi -> lo distance in
+ * elements, the number of valid entries (even; images start on even positions).  The launch packs the n_active blocks listed
+ * in `active`; n_entries (their valid entries) only feeds the profiler's byte count. */
+int ebfi_pack_pairs_block(void);
+int ebfi_pack_pairs_bf16(const float *src, const int32_t *table, const void *desc, const int32_t *active, int64_t n_active,
+                         int64_t n_entries, void *out, void *stream);
 
 /* 3x3, stride 1, padding 1, Cout <= 3, 16 <= Cin <= 64, >= 64 K output pixels (the model's last convolution 64 -> 3 + sigmoid,
  * ExposureDecision's 64 -> 1; reference model_misc/submodules.py:159-200 ConvLayer): Q[(co, tap)][p] = sum_ci w[co][ci][tap] x[ci][p]
@@ -574,6 +582,16 @@ int64_t ebfi_census_partials(int B, int H, int W);
 int ebfi_census_forward(const float *x, const float *y, float *partial, int B, int C, int H, int W, void *stream);
 int ebfi_census_backward(const float *x, const float *y, const float *grad_loss, float *grad_x,
                          int B, int C, int H, int W, void *stream);
+
+/* The two census terms of a training step (two predictions, one target) in one launch each way.  forward: partial holds
+ * 2 * ebfi_census_partials(B,H,W) floats, the per-tile sums of (xa, y) then of (xb, y), each exactly what ebfi_census_forward
+ * writes; a one-workgroup launch then adds them in a fixed order: loss[0] = wa * sum_a / (B*H*W) + wb * sum_b / (B*H*W).
+ * backward: grad_xa / grad_xb = what ebfi_census_backward gives for the 1-element gradient grad_loss[0] * wa / * wb, bit for
+ * bit.  xb == NULL: one prediction (loss[0] = wa * sum_a / (B*H*W); grad_xb is not touched). */
+int ebfi_census_pair_forward(const float *xa, const float *xb, const float *y, float wa, float wb, float *partial, float *loss,
+                             int B, int C, int H, int W, void *stream);
+int ebfi_census_pair_backward(const float *xa, const float *xb, const float *y, float wa, float wb, const float *grad_loss,
+                              float *grad_xa, float *grad_xb, int B, int C, int H, int W, void *stream);
 
 /* Laplacian-pyramid L1 term of the training loss for up to two predictions against one target
  * (loss/restore.py:166-213 LaplacianPyramid + LaplacianLoss: sum_i 2^i * L1sum(lap_i(pred), lap_i(target)), `levels` = 5;

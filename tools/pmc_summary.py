@@ -25,8 +25,8 @@ def load(d):
     for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
             name = r["Kernel_Name"]
-            m = re.search(r"(conv_[a-z0-9_]+|fac_[a-z_0-9]+|dcn_[a-z_0-9]+|gn_[a-z_]+|gauss5_[a-z_]+|census_[a-z_]+|src_[a-z_0-9]+|gather_sum_kernel|"
-                          r"grad_gather_kernel|pad2d_bwd_kernel|adam_flat_kernel|se_[a-z_]+|ed_[a-z_]+|lap_[a-z_]+|to_c16_kernel|pack_table_[a-z0-9_]+)", name)
+            m = re.search(r"(conv_[a-z0-9_]+|fac_[a-z_0-9]+|dcn_[a-z_0-9]+|gn_[a-z_]+|gauss5_[a-z_]+|census_[a-z_]+|census2_[a-z_]+|src_[a-z_0-9]+|gather_sum_kernel|"
+                          r"grad_gather_kernel|pad2d_bwd_kernel|adam_flat_kernel|se_[a-z_]+|ed_[a-z_]+|lap_[a-z_]+|to_c16_kernel|pack_table_[a-z0-9_]+|pack_pairs_[a-z0-9_]+)", name)
             if not m:
                 continue
             out[m.group(1)].append(float(r["Counter_Value"]) * 1024.0)
