@@ -41,6 +41,7 @@
  *   ebfi_period_frames_u8       GetFrames of the synthetic-blur reader (dataloader/h5dataset.py:296-311): sharp frames + exposure mean
  *   ebfi_event_cnt_image        event_visualisation.plot_event_cnt of the evaluation loop (infer_ours.py:139-142,
  *                               myutils/vis_events/matplotlib_plot_events.py:127-251)
+ *   ebfi_esim_*                 esim_py.EventSimulator of the dataset step (generate_dataset/syn_gopro.py:77-81,115-116)
  *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
  *   ebfi_lpips_*                perceptual_loss(net='alex') of the evaluation loop (loss/restore.py:10-40, LPIPS v0.1)
  *   ebfi_charbonnier_*          CharbonnierLoss of the validation loop (loss/restore.py:95-105, train_ours.py:588)
@@ -88,7 +89,8 @@ extern "C" {
  *      ebfi_duty_head_workspace / _forward / _backward (the duty head and MSE loss of the stage-1 pre-training), likewise; and
  *      ebfi_frames_u8_to_planar / ebfi_planar_to_u8 (the frame upload and download of an inference run on recorded clips); and
  *      ebfi_event_cnt_image_workspace / ebfi_event_cnt_image (the event-count images of the evaluation loop), likewise; and
- *      ebfi_period_frames_u8 (the sharp frames and the exposure mean of a training period from its stored bytes), likewise */
+ *      ebfi_period_frames_u8 (the sharp frames and the exposure mean of a training period from its stored bytes), likewise; and
+ *      ebfi_esim_loop_bound / _init / _count / _emit (the event simulator of the synthetic-dataset step), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -813,6 +815,56 @@ int64_t ebfi_event_cnt_image_workspace(int64_t n, int H, int W, int is_norm);
 int ebfi_event_cnt_image(const float *ev, const int64_t ev_strides[3], int64_t n, int H, int W, int color_scheme,
                          int is_black_background, int is_norm, int use_opencv, uint8_t *out, void *workspace,
                          int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ event simulator of the synthetic-dataset step
+ * What generate_dataset/syn_gopro.py:77-81,115-116 asks of esim_py.EventSimulator: events from a run of gray uint8 frames.  esim_py
+ * is not part of the reference tree; the law is stated here and restated in float64 numpy by tests/esim_ref.py, and the kernels
+ * are bit-identical to that restatement.
+ *
+ * levels: 256 float64 on the HOST, the level L[v] of byte v (log(log_eps + v / 255.0) or v / 255.0), made by the caller: the
+ * kernels never call log.  State per pixel, three float64 planes state[3][H][W] on the device: `it` (level of the last frame),
+ * `ref` (last crossing level), `last_t` (time of the last emitted event; 0.0 = none yet).  ebfi_esim_init sets it = ref =
+ * L[first frame], last_t = 0.  For each later frame at time T, dt = T - T_prev, itdt = L[v], all in float64:
+ *   if |it - itdt| > 1e-6:
+ *       pol = itdt >= it ? +1 : -1;  C = pol > 0 ? Cp : Cn;  cross = ref
+ *       repeat: cross = cross + pol * C
+ *               stop unless (pol > 0 and it < cross <= itdt) or (pol < 0 and it > cross >= itdt)
+ *               t = T_prev + ((cross - it) * dt) / (itdt - it)          multiply, divide, add: three roundings, never fused
+ *               if last_t == 0.0 or t - last_t >= refractory_period: emit (x, y, t, pol), last_t = t
+ *               ref = cross
+ *   it = itdt
+ * The repeat is a counted loop of ebfi_esim_loop_bound(levels, Cp, Cn) = ceil((max L - min L) / min(Cp, Cn)) + 1 rounds (every
+ * kept `cross` lies inside [min L, max L]), so no input can make a kernel spin.
+ *
+ * Frames: n later frames, uint8; pixel (k, y, x) at frames + k * frame_strides[0] + y * frame_strides[1] + x, or, with from_bgr,
+ * its three bytes B, G, R at ... + 3 * x and gray = (4899 R + 9617 G + 1868 B + 8192) >> 14.  times: n + 1 float64 on the HOST,
+ * times[0] the time of the frame the state stands at, times[k + 1] that of frame k, strictly increasing.  n <= EBFI_ESIM_MAX_CHUNK:
+ * levels and times travel as kernel arguments, a longer sequence is fed in chunks with the state carried.
+ *   ebfi_esim_count  walks the chunk from `state` WITHOUT writing it and stores counts[k][y][x] (int32), the number of events
+ *                    pixel (y, x) emits in interval k.
+ *   ebfi_esim_emit   takes the EXCLUSIVE prefix sums of counts (int64 offsets[k][y][x]), runs the identical walk, stores event e
+ *                    of (k, y, x) at index offsets[k][y][x] + e of xs / ys (int16), ts (float64), ps (int8, +-1), and writes
+ *                    the state back.  An index outside [0, capacity) is not stored (offsets that do not belong to the counts
+ *                    cannot write out of bounds).  The layout is [k][y][x][emission], exact and deterministic: no atomics.
+ * Output order of the law: (t, y, x, emission order within the pixel).  The emit layout is not yet that order, and a stable sort
+ * on t alone is not always enough: an event of interval k + 1 can round onto T_k+1, where another pixel may have an interval-k
+ * event exactly (linear levels and round thresholds produce both).  The caller sorts stably by pixel (y * W + x), then stably by t
+ * (ebfi_amd.esim does, over all chunks of a call).
+ * One lane owns one pixel, lanes run along x.  Each entry point is one launch on `stream`, no workspace, no host synchronisation;
+ * n == 0 is a no-op.
+ * Null pointers, n < 0 or > EBFI_ESIM_MAX_CHUNK, H or W outside [1, 32767], a negative stride, Cp or Cn below 1e-3, a non-finite
+ * parameter or level (log_eps <= 0), a negative refractory period, times not strictly increasing, a loop bound beyond 2^24 ->
+ * EBFI_ERR_ARG before anything touches the GPU (ebfi_esim_loop_bound returns -1 for them). */
+#define EBFI_ESIM_MAX_CHUNK 128
+int64_t ebfi_esim_loop_bound(const double *levels, double Cp, double Cn);
+int ebfi_esim_init(const uint8_t *frame, int64_t row_stride, int from_bgr, int H, int W, const double *levels, double *state,
+                   void *stream);
+int ebfi_esim_count(const uint8_t *frames, const int64_t frame_strides[2], int from_bgr, int64_t n, int H, int W,
+                    const double *times, const double *levels, double Cp, double Cn, double refractory_period,
+                    const double *state, int32_t *counts, void *stream);
+int ebfi_esim_emit(const uint8_t *frames, const int64_t frame_strides[2], int from_bgr, int64_t n, int H, int W,
+                   const double *times, const double *levels, double Cp, double Cn, double refractory_period, double *state,
+                   const int64_t *offsets, int64_t capacity, int16_t *xs, int16_t *ys, double *ts, int8_t *ps, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
