@@ -2371,9 +2371,11 @@ double conv_bytes_wgrad(const ConvGeom &g, int kk, bool dact, bool side_out) {
                   (double)g.Cout * g.Cin * kk);
 }
 
-int make_geom(ConvGeom &g, int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad) {
+// fwd5: the caller is the exact-fp32 forward, the one place a 5x5 (stride 1) kernel exists
+int make_geom(ConvGeom &g, int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad, bool fwd5 = false) {
     if (B < 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return fail(EBFI_ERR_ARG, "conv2d: non-positive dimension");
-    if (ks != 1 && ks != 3 && ks != 7) return fail(EBFI_ERR_UNSUPPORTED, "conv2d: kernel size %d (1, 3 and 7 implemented)", ks);
+    if (ks != 1 && ks != 3 && ks != 7 && !(fwd5 && ks == 5 && stride == 1))
+        return fail(EBFI_ERR_UNSUPPORTED, "conv2d: kernel size %d (1, 3 and 7 implemented; 5 in the fp32 stride-1 forward)", ks);
     if (stride != 1 && stride != 2) return fail(EBFI_ERR_UNSUPPORTED, "conv2d: stride %d (1 and 2 implemented)", stride);
     if (pad < 0 || pad > ks) return fail(EBFI_ERR_ARG, "conv2d: padding %d out of range", pad);
     g = ConvGeom{B, Cin, H, W, Cout, (H + 2 * pad - ks) / stride + 1, (W + 2 * pad - ks) / stride + 1, pad};
@@ -2389,7 +2391,8 @@ int make_geom(ConvGeom &g, int B, int Cin, int H, int W, int Cout, int ks, int s
 template <int KS, int S, bool TR, int DACT>
 int launch_fwd_d(hipStream_t st, const float *x, const float *dact_y, const float *w, const float *bias, float *out,
                  const ConvGeom &g, int act, float slope, float dslope) {
-    constexpr int CK = KS == 7 ? 2 : 8;      // input channels staged per chunk (LDS budget of the weight slice)
+    // input channels staged per chunk (LDS budget of the weight slice: 5x5 at 8 would take 69 KB, at 4 it takes 35 KB)
+    constexpr int CK = KS == 7 ? 2 : (KS == 5 ? 4 : 8);
     const int64_t tiles = (int64_t)g.B * ceil_div(g.Ho, TY) * ceil_div(g.Wo, TX);
     if (tiles > 2147483647LL) return fail(EBFI_ERR_ARG, "conv2d: too many tiles");
     const char *name = TR ? "conv_fwd_f32/dgrad" : "conv_fwd_f32/fwd";   // one kernel, two roles
@@ -3483,12 +3486,13 @@ extern "C" int ebfi_conv2d_forward(const void *input, const void *weight, const 
     if (dtype != EBFI_F32) return fail(EBFI_ERR_UNSUPPORTED, "conv2d_forward: dtype %d not implemented (fp32 only)", dtype);
     if (act < 0 || act > 2) return fail(EBFI_ERR_ARG, "conv2d_forward: unknown activation %d", act);
     ConvGeom g;
-    if (int rc = make_geom(g, B, Cin, H, W, Cout, ksize, stride, pad)) return rc;
+    if (int rc = make_geom(g, B, Cin, H, W, Cout, ksize, stride, pad, true)) return rc;
     if (B == 0) return EBFI_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float *x = static_cast<const float *>(input), *w = static_cast<const float *>(weight);
     const float *bs = static_cast<const float *>(bias);
     float *o = static_cast<float *>(output);
+    if (ksize == 5 && stride == 1) return launch_fwd<5, 1, false>(st, x, nullptr, w, bs, o, g, act, slope, 0, 0.f);
     if (ksize == 3 && stride == 1) return launch_fwd<3, 1, false>(st, x, nullptr, w, bs, o, g, act, slope, 0, 0.f);
     if (ksize == 3 && stride == 2) return launch_fwd<3, 2, false>(st, x, nullptr, w, bs, o, g, act, slope, 0, 0.f);
     if (ksize == 1 && stride == 1) return launch_fwd<1, 1, false>(st, x, nullptr, w, bs, o, g, act, slope, 0, 0.f);

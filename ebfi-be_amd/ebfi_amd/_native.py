@@ -160,6 +160,12 @@ SIGNATURES = {
     "ebfi_esim_count": (_i, [_vp, _p64, _i, _i64, _i, _i, _vp, _vp, _c.c_double, _c.c_double, _c.c_double, _vp, _vp, _vp]),
     "ebfi_esim_emit": (_i, [_vp, _p64, _i, _i64, _i, _i, _vp, _vp, _c.c_double, _c.c_double, _c.c_double, _vp, _vp, _i64,
                             _vp, _vp, _vp, _vp, _vp]),
+    "ebfi_avgpool2_forward": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ebfi_bilinear_up2_forward": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ebfi_flow_max_magnitude": (_i, [_vp, _i, _i, _vp, _vp]),
+    "ebfi_slomo_assemble": (_i, [_vp, _vp, _vp, _c.c_double, _vp, _i, _i, _vp]),
+    "ebfi_slomo_blend": (_i, [_vp, _vp, _c.c_double, _vp, _vp, _i, _i, _vp]),
+    "ebfi_slomo_frame_u8": (_i, [_vp, _vp, _i, _i, _vp]),
     "ebfi_prof_enable": (None, [_i]),
     "ebfi_prof_set_capacity": (_i, [_i]),
     "ebfi_prof_reset": (None, []),

@@ -42,6 +42,8 @@
  *   ebfi_event_cnt_image        event_visualisation.plot_event_cnt of the evaluation loop (infer_ours.py:139-142,
  *                               myutils/vis_events/matplotlib_plot_events.py:127-251)
  *   ebfi_esim_*                 esim_py.EventSimulator of the dataset step (generate_dataset/syn_gopro.py:77-81,115-116)
+ *   ebfi_avgpool2_forward / ebfi_bilinear_up2_forward / ebfi_flow_max_magnitude / ebfi_slomo_*
+ *                               the Vid2E adaptive upsampler (generate_dataset/upsampling/utils/{upsampler,model}.py)
  *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
  *   ebfi_lpips_*                perceptual_loss(net='alex') of the evaluation loop (loss/restore.py:10-40, LPIPS v0.1)
  *   ebfi_charbonnier_*          CharbonnierLoss of the validation loop (loss/restore.py:95-105, train_ours.py:588)
@@ -90,7 +92,9 @@ extern "C" {
  *      ebfi_frames_u8_to_planar / ebfi_planar_to_u8 (the frame upload and download of an inference run on recorded clips); and
  *      ebfi_event_cnt_image_workspace / ebfi_event_cnt_image (the event-count images of the evaluation loop), likewise; and
  *      ebfi_period_frames_u8 (the sharp frames and the exposure mean of a training period from its stored bytes), likewise; and
- *      ebfi_esim_loop_bound / _init / _count / _emit (the event simulator of the synthetic-dataset step), likewise */
+ *      ebfi_esim_loop_bound / _init / _count / _emit (the event simulator of the synthetic-dataset step), likewise; and
+ *      ebfi_avgpool2_forward / ebfi_bilinear_up2_forward / ebfi_flow_max_magnitude / ebfi_slomo_assemble / _blend / _frame_u8
+ *      (the frame-upsampling step), likewise -- with them ebfi_conv2d_forward accepts ksize 5 at stride 1, which it refused */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -177,7 +181,8 @@ int ebfi_dcn_backward(const void *input, const void *weight, const void *bias, c
  * What the reference gets from nn.Conv2d + nn.LeakyReLU / nn.Sigmoid inside ConvLayer
  * (models/model_misc/submodules.py:159-200).  Contiguous NCHW fp32.
  *   input [B,Cin,H,W]  weight [Cout,Cin,k,k]  bias [Cout] or NULL  output [B,Cout,Ho,Wo]
- *   k in {1,3}, stride in {1,2}, Ho = (H + 2*pad - k)/stride + 1.
+ *   k in {1,3}, stride in {1,2}, Ho = (H + 2*pad - k)/stride + 1.  (ebfi_conv2d_forward also: k = 7 at stride 1 and 2, and
+ *   k = 5 at stride 1 -- the Super-SloMo U-Net's second stage; the gradients and the bf16 forms refuse k = 5.)
  *   act: 0 none, 1 LeakyReLU(slope), 2 Sigmoid -- fused into the epilogue. */
 int ebfi_conv2d_forward(const void *input, const void *weight, const void *bias, void *output,
                         int B, int Cin, int H, int W, int Cout, int ksize, int stride, int pad,
@@ -865,6 +870,47 @@ int ebfi_esim_count(const uint8_t *frames, const int64_t frame_strides[2], int f
 int ebfi_esim_emit(const uint8_t *frames, const int64_t frame_strides[2], int from_bgr, int64_t n, int H, int W,
                    const double *times, const double *levels, double Cp, double Cn, double refractory_period, double *state,
                    const int64_t *offsets, int64_t capacity, int16_t *xs, int16_t *ys, double *ts, int8_t *ps, void *stream);
+
+/* ------------------------------------------------------------------ frame upsampling (adaptive Super-SloMo)
+ * What generate_dataset/upsampling/utils/upsampler.py and model.py compute between the convolutions of their two U-Nets, at
+ * batch 1 on planar float32 tensors [C, H, W] (csrc/upsample.hip; restated in float64 by tests/upsample_ref.py).  All run on
+ * `stream`; none allocates or synchronises.
+ *
+ *   ebfi_avgpool2_forward      out[c][y][x] = mean of the 2 x 2 block of x [C, H, W] (H, W even)  -> [C, H/2, W/2]
+ *   ebfi_bilinear_up2_forward  bilinear x2 with align_corners = True: source coordinate o * (n - 1) / (2n - 1), computed in
+ *                              float32; a 1 x 1 map is copied to 2 x 2                             -> [C, 2H, 2W]
+ *   ebfi_flow_max_magnitude    flow [4, H, W] = (F_0_1, F_1_0): *out = max over both of sqrt(u*u + v*v) in float32 (sum and sqrt
+ *                              rounded separately).  A selection: the result is one of the magnitudes, whatever the order of
+ *                              the reduction.  A NaN anywhere gives NaN.  The caller's N is ceil(*out).
+ *
+ * Back-warp of `img` by a flow (u, v), the reference's backWarp: at pixel (gx, gy) the coordinate x = 2 * ((gx + u) / W - 0.5),
+ * likewise y with H, sampled by grid_sample(bilinear, zero padding, align_corners = True), i.e. at the pixel position
+ * ((x + 1) / 2) * (W - 1) -- (gx + u) * (W - 1) / W up to rounding, so zero flow is NOT the identity.  Corners outside the image
+ * contribute zero.
+ *
+ *   ebfi_slomo_assemble  with t in (0, 1) and, from Python doubles rounded to float32, c = -t(1-t):
+ *                          F_t_0 = c F_0_1 + t^2 F_1_0,  F_t_1 = (1-t)^2 F_0_1 + c F_1_0
+ *                        out20 [20, H, W] = I0 (3) | I1 (3) | F_0_1 (2) | F_1_0 (2) | F_t_1 (2) | F_t_0 (2) | warp(I1, F_t_1) (3)
+ *                        | warp(I0, F_t_0) (3): the interpolation network's input.
+ *   ebfi_slomo_blend     intrp [5, H, W] = that network's output, x20 = what assemble wrote:
+ *                          F_t_0_f = intrp[0:2] + F_t_0, F_t_1_f = intrp[2:4] + F_t_1, V0 = sigmoid(intrp[4]), V1 = 1 - V0,
+ *                          Ft_p = ((1-t) V0 warp(I0, F_t_0_f) + t V1 warp(I1, F_t_1_f)) / ((1-t) V0 + t V1)
+ *                        rgb [3, H, W] (may be NULL) = Ft_p + mean; gray [H, W] = the byte law of that frame.
+ *   ebfi_slomo_frame_u8  the byte law alone, of a normalised frame [3, H, W] (the reference writes I0 through it as well).
+ *
+ * Byte law, per channel c (RGB) in float32, each step rounded: m = v + mean[c] (mean = 0.429, 0.431, 0.397); s = 255 * m;
+ * clip to [0, 255]; truncate to an integer level l[c] (a NaN gives 0).  gray = (3735 l[0] + 19235 l[1] + 9798 l[2] + 16384) >> 15:
+ * OpenCV 4's 8-bit cvtColor(BGR2GRAY) as read from its source, NOT checked against a cv2 build; the reference passes its RGB
+ * frame under the BGR code, so R takes the blue coefficient.
+ *
+ * assemble and blend need W % 4 == 0, H, W >= 2 and 16-byte aligned float tensors (gray: 4-byte); the others take any size.
+ * Null pointers, non-positive or odd (pool) sizes, 2^31 elements or more, t outside (0, 1) -> EBFI_ERR_ARG. */
+int ebfi_avgpool2_forward(const float *x, float *out, int C, int H, int W, void *stream);
+int ebfi_bilinear_up2_forward(const float *x, float *out, int C, int H, int W, void *stream);
+int ebfi_flow_max_magnitude(const float *flow, int H, int W, float *out, void *stream);
+int ebfi_slomo_assemble(const float *I0, const float *I1, const float *flow, double t, float *out20, int H, int W, void *stream);
+int ebfi_slomo_blend(const float *intrp, const float *x20, double t, float *rgb, uint8_t *gray, int H, int W, void *stream);
+int ebfi_slomo_frame_u8(const float *frame, uint8_t *gray, int H, int W, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
