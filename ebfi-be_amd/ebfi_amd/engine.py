@@ -8,6 +8,7 @@ import contextlib
 
 import torch
 
+from . import graphstep
 from .dp import FlatAdam, FlatGradBucket, broadcast_parameters
 from .loss import TrainLoss
 from .model import EVFIAutoEx
@@ -81,11 +82,11 @@ def synthetic_validation_batch(B, H, W, TB=16, num_frames=4, device="cuda", seed
     return tuple(v.to(device) for v in (frame, event, ts, gtex, latent))
 
 
-class Engine:
+class Engine(graphstep.GraphStepper):
     def __init__(self, model_args=None, device="cuda", precision="fp32", lr=1e-4, seed=None, train=True, graph=False,
                  accu_step=1, betas=(0.9, 0.999), backward_f16=None, forward_f16="filters", strict_graph=None):
-        """strict_graph: a hipGraph capture that fails raises instead of continuing with eager launches.  Default: on when
-        the process is one rank of several (a rank that silently runs ~20 % slower drags every rank of the job), off alone.
+        """graph / accu_step / strict_graph: see graphstep.GraphStepper (a graph is captured per input shape, precision and loss
+        phase).
         forward_f16 (only with the fp16 backward; ignored otherwise): which FORWARD convolutions read fp16 operand images (one matrix-core product per
         tap, fp32 accumulation) instead of running in split precision:
           "filters"  the 128 -> 1600 KernelConv of Modification, whose output exists only as fp16 planes anyway (ebfi_amd.fac):
@@ -101,34 +102,18 @@ class Engine:
         test_benchmarked_step_vs_oracle); False restores the split-precision backward."""
         if precision not in ("fp32", "bf16x3", "bf16"):
             raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
-        self.device = torch.device(device)
+        super().__init__(device, graph=graph, accu_step=accu_step, strict_graph=strict_graph)
         self.precision = precision
         if seed is not None:
             torch.manual_seed(seed)
         self.model_args = dict(DEFAULT_MODEL_ARGS, **(model_args or {}))
         self.model = EVFIAutoEx(**self.model_args).to(self.device)
         broadcast_parameters(self.model, 0)
-        self.iteration = 0                                  # optimiser steps taken (the reference's train_iter_idx)
-        # gradient accumulation (trainer.accu_step, train_ours.py:206,259-277): every call of train_step is one
-        # forward+backward on loss / accu_step; the all-reduce and the optimiser step happen on every accu_step-th call
-        self.accu_step = max(1, int(accu_step))
-        self._micro = 0
         # fp16 backward: the first optimiser steps of a run measure every operand scale just in time (eager launches).  The
         # x0.1 initialisation leaves activations at 1e-18 in the deep stacks; the first Adam update (every weight and bias
         # moves by lr) lifts them to 1e-4 -- fourteen decades in one step, which no one-step-old scale survives.  From the
         # third step on magnitudes move by a few percent per step and the delayed scales (f16scale) take over.
         self.calibration_steps = 2
-        self._steps_run = 0
-        self._accum = None
-        # graph=True: forward + loss + backward + gradient packing are captured once into a hipGraph (per input shape,
-        # precision and loss phase) and replayed; the all-reduce and the optimiser step stay eager (train_step_graph).
-        self.use_graph = bool(graph) and self.device.type == "cuda"
-        self._graphs = {}
-        self.graph_capture_failed, self.graph_capture_error = False, None    # set when a capture fell back to eager launches
-        if strict_graph is None:
-            from .dp import is_distributed
-            strict_graph = is_distributed()
-        self.strict_graph = bool(strict_graph)
         if train:
             self.model.train()
             self.loss = TrainLoss(self.model_args.get("DetailEnabled", True)).to(self.device)
@@ -165,34 +150,6 @@ class Engine:
             self.bank.pack_on_demand = True
             self.book.forward_f16 = forward_f16
 
-    @property
-    def settled(self):
-        """True once the steps that are not the steady state are over: the just-in-time calibration steps of the fp16 backward
-        and, with graph=True, the capture.  (Throughput loggers start their clock here.)"""
-        if self.book is not None and self.precision == "bf16x3" and self._steps_run < self.calibration_steps:
-            return False
-        return not self.use_graph or bool(self._graphs)
-
-    @contextlib.contextmanager
-    def _autocast(self):
-        """precision 'bf16' = bf16 matrix-core operands for the 3x3 / 1x1 convs (fp32 storage and
-        accumulation, ebfi_amd.conv); everything else, and precision 'fp32', computes in fp32."""
-        from . import conv
-        prev = conv.get_compute_dtype()
-        conv.set_compute_dtype(self.precision)
-        try:
-            yield
-        finally:
-            conv.set_compute_dtype(prev)
-
-    def _bank(self):
-        """Context of one pass: the weight bank refreshed (ONE pack launch, captured with the step's graph) and active
-        while the split-precision mode runs; a no-op otherwise."""
-        if self.bank is None or self.precision != "bf16x3":
-            return contextlib.nullcontext()
-        self.bank.refresh()
-        return self.bank.active()
-
     def _book(self):
         """Context of one pass: the fp16 backward kernels active on the scale book (a no-op without one)."""
         if self.book is None or self.precision != "bf16x3":
@@ -221,110 +178,18 @@ class Engine:
     def _guard(self):
         return self.book.guard if (self.book is not None and self.precision == "bf16x3") else None
 
-    def _finish_micro_step(self, wire):
-        """`wire`: this call's packed gradient (of loss / accu_step) with the overflow flag behind it (FlatGradBucket.wire).
-        Sums the calls of one accumulation window in place and, on the window's last call, averages over ranks -- ONE
-        collective: the flag travels with the gradients -- and takes the optimiser step.  True when a step was taken."""
-        if self.accu_step > 1:
-            if self._micro == 0:
-                self._accum = wire.clone() if self._accum is None else self._accum.copy_(wire)
-            else:
-                self._accum.add_(wire)           # (the flags add up too: > 0 if any micro-step raised the guard)
-            self._micro += 1
-            if self._micro < self.accu_step:
-                return False
-            self._micro = 0
-            wire = self._accum
-        self.bucket.adopt(wire)
-        self.bucket.reduce_mean_packed()
-        guard = self._guard()
-        self.optimizer.step(self.bucket.flat, guard=guard, flag=self.bucket.flag if guard is not None else None)
-        self.iteration += 1
-        self._steps_run += 1
-        return True
+    def _calibrating(self):
+        """The just-in-time calibration steps of the fp16 backward (see __init__): eager launches."""
+        return self.book is not None and self.precision == "bf16x3" and self._steps_run < self.calibration_steps
 
-    def train_step(self, frame, event, t, gtex, target):
-        """One forward+backward on this rank's batch (plus, every `accu_step`-th call, the gradient all-reduce and the
-        optimiser step); returns the (unreduced) loss tensor, already divided by accu_step like the reference's."""
-        calibrating = self.book is not None and self.precision == "bf16x3" and self._steps_run < self.calibration_steps
-        if self.use_graph and not calibrating:
-            return self.train_step_graph(frame, event, t, gtex, target)
-        self._begin_micro_step()
-        self.bucket.zero()
-        loss = self._fwd_bwd(frame, event, t, gtex, target)
-        self.bucket.gather(self._guard())
-        self._finish_micro_step(self.bucket.wire)
-        return loss
+    def _graph_key(self):
+        return (self.iteration < 10e3,)                    # TrainLoss switches its weighting at 10k iterations
 
-    def train_step_graph(self, frame, event, t, gtex, target):
-        """Same step with the ~560 launches of forward + loss + backward + gradient packing replayed from one
-        hipGraph.  Inputs are copied into static buffers; gradients live in the graph's memory pool, `param.grad`
-        are views of the packed buffer, so the eager all-reduce / Adam that follow see ordinary tensors."""
-        inputs = (frame, event, t, gtex, target)
-        phase = self.iteration < 10e3                      # TrainLoss switches its weighting at 10k iterations
-        key = (self.precision, phase, self.accu_step) + tuple((tuple(v.shape), v.dtype) for v in inputs)
-        entry = self._graphs.get(key)
-        if entry is None:
-            static_in = [torch.empty_like(v) for v in inputs]
-            for s, v in zip(static_in, inputs):
-                s.copy_(v)
-            # The warm-up passes and the capture run _fwd_bwd -> book.finish() outside any accumulation window: a flag they
-            # raise (or their three advances of the delayed scales on one batch) must not leak into the window this call
-            # belongs to -- with accu_step > 1 the capture can happen mid-window, where nothing clears the guard afterwards
-            # (round-4 advisory).  The guard words are restored after the capture; the scales keep what the warm-up passes
-            # measured on this batch (restoring them could undo the just-in-time calibration of a slot first met here).
-            guard = self._guard()
-            saved = None if guard is None else guard.clone()
-            if self.bank is not None and not self._graphs:
-                # the bf16 images the steady state reads are those the warm-up passes below ask for, not what the calibration
-                # steps asked for on their way (a later shape's capture only adds to the set: earlier graphs replay its prefix)
-                self.bank.forget_requests()
-            side = torch.cuda.Stream(self.device)          # warm-up off the default stream (allocator, lazy inits)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self.bucket.zero()
-                    self._fwd_bwd(*static_in)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            self.bucket.zero()
-            graph = torch.cuda.CUDAGraph()
-            try:
-                # thread_local: another thread of the process (the RCCL watchdog polling its events) must not
-                # invalidate the capture
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    loss = self._fwd_bwd(*static_in)
-                    self.bucket.gather(guard)
-                    wire = self.bucket.wire
-            except RuntimeError as err:
-                if saved is not None:
-                    torch.cuda.synchronize(self.device)
-                    guard.copy_(saved)
-                if self.strict_graph:
-                    raise RuntimeError("ebfi_amd.engine: hipGraph capture failed and strict_graph is set (the default for one "
-                                       "rank of several): %s" % str(err).splitlines()[0]) from err
-                # a capture that cannot be taken must not cost the run: say so and continue with eager launches
-                import sys
-                print("ebfi_amd.engine: hipGraph capture failed (%s); continuing with eager launches" % str(err).splitlines()[0],
-                      file=sys.stderr, flush=True)
-                self.use_graph = False
-                self.graph_capture_failed, self.graph_capture_error = True, str(err).splitlines()[0]
-                torch.cuda.synchronize(self.device)
-                return self.train_step(frame, event, t, gtex, target)
-            if saved is not None:
-                guard.copy_(saved)
-            entry = (graph, static_in, loss, wire, [p.grad for p in self.bucket.params])
-            self._graphs[key] = entry
-        graph, static_in, loss, wire, grads = entry
-        self._begin_micro_step()
-        for s, v in zip(static_in, inputs):
-            if s.data_ptr() != v.data_ptr():
-                s.copy_(v)
-        graph.replay()
-        self.bucket.adopt(wire)
-        for p, g in zip(self.bucket.params, grads):        # (another shape's graph may have re-pointed them)
-            p.grad = g
-        self._finish_micro_step(wire)
-        return loss.clone()
+    def _before_first_capture(self):
+        if self.bank is not None:
+            # the bf16 images the steady state reads are those the warm-up passes of the capture ask for, not what the calibration
+            # steps asked for on their way (a later shape's capture only adds to the set: earlier graphs replay its prefix)
+            self.bank.forget_requests()
 
     @torch.no_grad()
     def infer(self, frame, event, t, gtex=None):
@@ -534,17 +399,10 @@ class ClipInterpolator:
                 t_static = torch.zeros(k * B, 1, device=dev)
                 call = (lambda: self.model.decode(tuple(st_in), t_static)[-1]) if self.hoist else \
                     (lambda: self.model(st_in[0], st_in[1], t_static, st_in[2])[-1])
-                side = torch.cuda.Stream(dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    call()                                  # warm-up off the capturing stream (allocator, lazy inits)
-                torch.cuda.current_stream(dev).wait_stream(side)
-                g = torch.cuda.CUDAGraph()
                 try:
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        out_static = call()
+                    g, out_static = graphstep.capture(call, dev, 1)
                 except RuntimeError as err:
-                    # as Engine.train_step_graph: say so and continue with eager launches (the flag is there for callers)
+                    # as GraphStepper.train_step_graph: say so and continue with eager launches (the flag is there for callers)
                     import sys
                     print("ebfi_amd.engine: hipGraph capture of the inference step failed (%s); continuing with eager launches"
                           % str(err).splitlines()[0], file=sys.stderr, flush=True)

@@ -6,14 +6,13 @@ model.args.LoadPretrainEX / PretrainedEXPath and optionally freezes it (FrozenEX
 
 A step = blur-level map on the device -> ExposureDecision up to Conv1 -> duty head + MSE as ONE native node
 (ebfi_amd.loss.DutyMSELoss, csrc/dutyhead.hip) -> backward -> gradient packing -> ONE flat all-reduce -> one Adam launch: the
-optimiser path of the main engine (ebfi_amd.dp).  `Engine` itself is not involved.
+optimiser path of the main engine (ebfi_amd.graphstep.GraphStepper over ebfi_amd.dp).  `Engine` itself is not involved.
 """
-import contextlib
-
 import torch
 
 from .blur import Frame2DCP, Frame2Lap
 from .dp import FlatAdam, FlatGradBucket, broadcast_parameters
+from .graphstep import GraphStepper
 from .loss import DutyMSELoss, duty_head
 from .model import ExposureDecision
 
@@ -74,18 +73,20 @@ def synthetic_exposure_batch(B, H, W, TB=16, exposure_time=(1, 2, 3, 4, 5, 6, 7,
     return tuple(v.to(device) for v in (frame, event, times[pick].reshape(B, 1)))
 
 
-class ExposureEngine:
+class ExposureEngine(GraphStepper):
     VALID_KEYS = ("valid_loss", "valid_mae")
 
     def __init__(self, model_args=None, fashion="RGBLap", device="cuda", precision="fp32", lr=1e-4, seed=None, graph=False,
                  accu_step=1, betas=(0.9, 0.999), strict_graph=None, name="ExposureDecision"):
         """precision: 'fp32' (exact) or 'bf16x3' (split-precision matrix-core operands, fp32-grade accuracy) for the 3x3
-        convolutions; the fp16-operand backward of the main engine is not used here.  graph / strict_graph: as Engine."""
+        convolutions; the fp16-operand backward of the main engine is not used here.  graph / accu_step / strict_graph: see
+        graphstep.GraphStepper."""
         check_model_name(name)
         if precision not in ("fp32", "bf16x3"):
             raise ValueError("precision must be 'fp32' or 'bf16x3'")
         self.fashion = check_fashion(fashion)
-        self.device = torch.device(device)
+        # every period of a load is one micro-step on loss / accu_step; all-reduce and Adam on every accu_step-th (:252-259)
+        super().__init__(device, graph=graph, accu_step=accu_step, strict_graph=strict_graph)
         self.precision = precision
         if seed is not None:
             torch.manual_seed(seed)
@@ -96,48 +97,14 @@ class ExposureEngine:
         self.model = ExposureDecision(**self.model_args).to(self.device)
         broadcast_parameters(self.model, 0)
         self.model.train()
-        self.iteration = 0                                  # optimiser steps taken (the reference's train_iter_idx)
         self.last_Ex = None
-        # every period of a load is one micro-step on loss / accu_step; all-reduce and Adam on every accu_step-th (:252-259)
-        self.accu_step = max(1, int(accu_step))
-        self._micro = 0
-        self._accum = None
         self.loss = DutyMSELoss(1.0 / self.accu_step)
         self.bucket = FlatGradBucket(self.model)
         self.optimizer = FlatAdam(self.bucket.params, lr=lr, betas=tuple(betas))
-        self.use_graph = bool(graph) and self.device.type == "cuda"
-        self._graphs = {}
-        self.graph_capture_failed, self.graph_capture_error = False, None
-        if strict_graph is None:
-            from .dp import is_distributed
-            strict_graph = is_distributed()
-        self.strict_graph = bool(strict_graph)
         self.bank = None
         if self.device.type == "cuda" and precision == "bf16x3":
             from . import weightbank
             self.bank = weightbank.build_for(self.model, flat=self.optimizer.flat.data, params=self.optimizer.params)
-
-    @property
-    def settled(self):
-        return not self.use_graph or bool(self._graphs)
-
-    @contextlib.contextmanager
-    def _mode(self, refresh=True):
-        """One pass in the engine's precision: the conv kernels' compute mode set and restored, the weight bank refreshed (one
-        pack launch, captured with the step's graph) and active in split precision."""
-        from . import conv
-        prev = conv.get_compute_dtype()
-        conv.set_compute_dtype(self.precision)
-        try:
-            if self.bank is not None:
-                if refresh:
-                    self.bank.refresh()
-                with self.bank.active():
-                    yield
-            else:
-                yield
-        finally:
-            conv.set_compute_dtype(prev)
 
     def inputs(self, frame, event):
         """(Event viewed as [B, 2*TB, H, W], BlurryLevel) of one period."""
@@ -145,96 +112,22 @@ class ExposureEngine:
         return event, blurry_level(frame, self.fashion)
 
     def _fwd_bwd(self, frame, event, duty):
-        with self._mode():
+        with self._autocast(), self._bank():
             ev, bl = self.inputs(frame, event)
             loss = self.loss(self.model.ex_map(ev, bl), duty)
             loss.backward()
         return loss.detach(), self.loss.Ex
 
-    def _finish_micro_step(self, wire):
-        """Sums the calls of one accumulation window and, on its last call, averages over ranks (one collective) and takes
-        the optimiser step.  True when a step was taken."""
-        if self.accu_step > 1:
-            if self._micro == 0:
-                self._accum = wire.clone() if self._accum is None else self._accum.copy_(wire)
-            else:
-                self._accum.add_(wire)
-            self._micro += 1
-            if self._micro < self.accu_step:
-                return False
-            self._micro = 0
-            wire = self._accum
-        self.bucket.adopt(wire)
-        self.bucket.reduce_mean_packed()
-        self.optimizer.step(self.bucket.flat)
-        self.iteration += 1
-        return True
-
-    def train_step(self, frame, event, duty):
-        """One forward+backward on this rank's period (plus, every `accu_step`-th call, the gradient all-reduce and the
-        optimiser step); returns the (unreduced) loss, already divided by accu_step like the reference's.  `last_Ex` holds
-        the [B, 1] estimate of this call."""
-        if self.use_graph:
-            return self.train_step_graph(frame, event, duty)
-        self.bucket.zero()
-        loss, self.last_Ex = self._fwd_bwd(frame, event, duty)
-        self.bucket.gather()
-        self._finish_micro_step(self.bucket.wire)
-        return loss
-
-    def train_step_graph(self, frame, event, duty):
-        """The same step with forward + loss + backward + gradient packing replayed from one hipGraph per input shape; the
-        all-reduce and the optimiser step stay eager (as Engine.train_step_graph)."""
-        inputs = (frame, event, duty)
-        key = (self.precision, self.accu_step) + tuple((tuple(v.shape), v.dtype) for v in inputs)
-        entry = self._graphs.get(key)
-        if entry is None:
-            static_in = [torch.empty_like(v) for v in inputs]
-            for s, v in zip(static_in, inputs):
-                s.copy_(v)
-            side = torch.cuda.Stream(self.device)          # warm-up off the default stream (allocator, lazy inits)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self.bucket.zero()
-                    self._fwd_bwd(*static_in)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            self.bucket.zero()
-            graph = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    loss, ex = self._fwd_bwd(*static_in)
-                    self.bucket.gather()
-                    wire = self.bucket.wire
-            except RuntimeError as err:
-                if self.strict_graph:
-                    raise RuntimeError("ebfi_amd.exposure_engine: hipGraph capture failed and strict_graph is set (the default for "
-                                       "one rank of several): %s" % str(err).splitlines()[0]) from err
-                import sys
-                print("ebfi_amd.exposure_engine: hipGraph capture failed (%s); continuing with eager launches"
-                      % str(err).splitlines()[0], file=sys.stderr, flush=True)
-                self.use_graph = False
-                self.graph_capture_failed, self.graph_capture_error = True, str(err).splitlines()[0]
-                torch.cuda.synchronize(self.device)
-                return self.train_step(frame, event, duty)
-            entry = (graph, static_in, loss, ex, wire, [p.grad for p in self.bucket.params])
-            self._graphs[key] = entry
-        graph, static_in, loss, ex, wire, grads = entry
-        for s, v in zip(static_in, inputs):
-            if s.data_ptr() != v.data_ptr():
-                s.copy_(v)
-        graph.replay()
-        self.bucket.adopt(wire)
-        for p, g in zip(self.bucket.params, grads):        # (another shape's graph may have re-pointed them)
-            p.grad = g
-        self._finish_micro_step(wire)
-        self.last_Ex = ex.clone()
-        return loss.clone()
+    def _publish(self, out, static):
+        """`last_Ex` holds the [B, 1] estimate of this call."""
+        loss, ex = out
+        self.last_Ex = ex.clone() if static else ex
+        return loss.clone() if static else loss
 
     @torch.no_grad()
     def predict(self, frame, event):
         """Ex [B, 1] of one period in the engine's precision (module forward, current weights)."""
-        with self._mode():
+        with self._autocast(), self._bank():
             return self.model(*self.inputs(frame, event))
 
     @torch.no_grad()
@@ -261,7 +154,7 @@ class ExposureEngine:
         try:
             loss = torch.zeros((), dtype=torch.float64, device=frames.device)
             mae = torch.zeros((), dtype=torch.float64, device=frames.device)
-            with self._mode():
+            with self._autocast(), self._bank():
                 for i in range(num_p):
                     duty = duties[:, i].reshape(-1, 1).float()
                     # (Ex through the native head's loss-free form: two launches instead of the pooling / sigmoid tail)

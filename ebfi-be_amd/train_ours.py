@@ -217,17 +217,27 @@ def add_loader_arguments(ap):
                          "ahead while the current batch trains; 0 = everything synchronously in the training loop")
 
 
+DEFAULT_EXPOSURE_TIME = [9, 10, 11, 12, 13, 14, 15]      # ExposureTime of the reference's train_ours.yml (Custom exposure)
+
+
+def clip_dataset(path, ds_cfg, time_bins, default_exposure_time, device, seed, loader):
+    """The recorded-clip dataset of both trainers, for training and validation alike: `ds_cfg` is a dataset section of the config
+    with the reference's keys (train_ours.yml:115-150); absent keys take its shipped values, `time_bins` and
+    `default_exposure_time` being the calling script's."""
+    from ebfi_amd import clipdata
+    return clipdata.ClipDataset(path, time_bins=int(ds_cfg.get("time_bins", time_bins)),
+                                frames_per_period=int(ds_cfg.get("NumFramePerPeriod", 16)),
+                                frames_per_blurry=int(ds_cfg.get("NumFramePerBlurry", 16)),
+                                exposure_method=ds_cfg.get("ExposureMethod", "Custom"),
+                                exposure_time=ds_cfg.get("ExposureTime", default_exposure_time),
+                                device=device, seed=seed, frames=loader, **clipdata.dataset_args_from_config(ds_cfg))
+
+
 def real_data_passes(path, config, B, TB, device, rank, world, seed, loader="device", prefetch=1):
     """Endless stream of (Frame, Event, T, GTEx, LatentF) passes from recorded clips (ebfi_amd.clipdata): the dataset keys
     are the reference's (config train_dataloader.dataset, train_ours.yml:115-150); defaults = its shipped values."""
     from ebfi_amd import clipdata
-    ds_cfg = ((config.get("train_dataloader") or {}).get("dataset") or {})
-    ds = clipdata.ClipDataset(path, time_bins=int(ds_cfg.get("time_bins", TB)),
-                              frames_per_period=int(ds_cfg.get("NumFramePerPeriod", 16)),
-                              frames_per_blurry=int(ds_cfg.get("NumFramePerBlurry", 16)),
-                              exposure_method=ds_cfg.get("ExposureMethod", "Custom"),
-                              exposure_time=ds_cfg.get("ExposureTime", [9, 10, 11, 12, 13, 14, 15]),
-                              device=device, seed=seed, frames=loader, **clipdata.dataset_args_from_config(ds_cfg))
+    ds = clip_dataset(path, (config.get("train_dataloader") or {}).get("dataset") or {}, TB, DEFAULT_EXPOSURE_TIME, device, seed, loader)
     if len(ds) < B * world:
         raise SystemExit("--data: %d periods in %s, need at least batch_size x world = %d" % (len(ds), path, B * world))
     for batch in clipdata.batches(ds, B, rank=rank, world=world, seed=seed, prefetch=prefetch):
@@ -244,12 +254,7 @@ def validation_batches(vs, config, args, B, H, W, TB, device, rank, world):
     ds_cfg = vs["dataset"]
     vb = vs["batch_size"] or B
     if vs["valid_data"]:
-        ds = clipdata.ClipDataset(vs["valid_data"], time_bins=int(ds_cfg.get("time_bins", TB)),
-                                  frames_per_period=int(ds_cfg.get("NumFramePerPeriod", 16)),
-                                  frames_per_blurry=int(ds_cfg.get("NumFramePerBlurry", 16)),
-                                  exposure_method=ds_cfg.get("ExposureMethod", "Custom"),
-                                  exposure_time=ds_cfg.get("ExposureTime", [9, 10, 11, 12, 13, 14, 15]),
-                                  device=device, seed=args.seed, frames=args.loader, **clipdata.dataset_args_from_config(ds_cfg))
+        ds = clip_dataset(vs["valid_data"], ds_cfg, TB, DEFAULT_EXPOSURE_TIME, device, args.seed, args.loader)
         if len(ds) == 0:
             raise SystemExit("--valid-data: no complete period in %s" % vs["valid_data"])
         return lambda: clipdata.eval_batches(ds, vb, rank=rank, world=world, seed=args.seed, drop_last=vs["drop_last"],
@@ -276,6 +281,62 @@ def run_validation(eng, batches, tracker, stamp, log_step=50, rank=0):
             if rank == 0 and k % log_step == 0:
                 print("Valid timestamp: %d [batch %d] valid_loss: %.4e" % (stamp, k, host[0]), flush=True)
     return tracker.result()
+
+
+def train_loop(eng, next_micro_batch, samples_per_pass, unit, st, vs, scheduler, monitor, valid_batches, tracker, out_dir, config,
+               rank, world, start):
+    """The iteration body of both trainers, from iteration `start` on: accu_step passes on `next_micro_batch(it, micro)`, log,
+    validate, monitor, checkpoint, early stop, scheduler gate.  samples_per_pass / unit: what one pass of one rank adds to the
+    logged rate and the word it is logged under ('frames' -> frames/s).  Returns the iteration count it ended at."""
+    # throughput is counted from the end of the first iteration after which the engine is in its steady state (the first ones
+    # pay module load, allocator growth, the just-in-time calibration of the fp16 operand scales and, with --graph, the
+    # capture: GraphStepper.settled): what is logged is the steady-state rate, whole job (all ranks)
+    t0, samples, it, valid_stamp = None, 0, start, 1
+    while it < st["iterations"]:
+        for micro in range(st["accu_step"]):
+            loss = eng.train_step(*next_micro_batch(it, micro))
+            if t0 is not None:
+                samples += samples_per_pass * world
+        log_now = it % st["log_step"] == 0 or it == st["iterations"] - 1
+        if log_now:                      # the loss all-reduce is for logging only (train_ours.py:278-279): do it when logging
+            loss = reduce_tensor(loss.clone())
+        lr_now = scheduler.get_last_lr()[0] if scheduler is not None else eng.optimizer.param_groups[0]["lr"]
+        if rank == 0 and log_now:
+            torch.cuda.synchronize()
+            rate = samples / (time.perf_counter() - t0) if t0 is not None and samples else float("nan")
+            print("Iteration: %d/%d train_loss: %.4e learning rate: %.4e  %.1f %s/s"
+                  % (it, st["iterations"], loss.item(), lr_now, rate, unit), flush=True)
+        if t0 is None and eng.settled:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        # validation every valid_step-th iteration, never at 0 (train_ours.py:309-328); all ranks take part and decide alike
+        best = stop = False
+        if vs["do_validation"] and it % vs["valid_step"] == 0 and it != 0:
+            t_valid = time.perf_counter()
+            val_log = run_validation(eng, valid_batches, tracker, valid_stamp, vs["valid_log_step"], rank)
+            if t0 is not None:           # (the logged rate is the training rate: the stamp's time is taken off the clock)
+                t0 += time.perf_counter() - t_valid
+            stop, best = monitor.evaluate(val_log)
+            if rank == 0:
+                print("Valid stamp: %d %s (best %r)" % (valid_stamp, " ".join("%s: %.6e" % (k, val_log[k]) for k in eng.VALID_KEYS),
+                                                        monitor.best), flush=True)
+                if stop:
+                    print(monitor.stop_message(), flush=True)
+            valid_stamp += 1
+        # periodic checkpoints as train_ours.py:331-333 (saved BEFORE this iteration's scheduler step, like there; also when this
+        # stamp is the best so far, then twice: :665-671), plus one after the last iteration -- the one an early stop ends at too
+        if rank == 0 and ((st["save_period"] and it % st["save_period"] == 0 and it != 0) or best or stop
+                          or it == st["iterations"] - 1):
+            path = os.path.join(out_dir, "checkpoint-iteration%d.pth" % it)
+            for p in save_checkpoint(path, eng, scheduler, config, it, monitor.best if monitor is not None else None, best):
+                print("saved", p, flush=True)
+        if stop:
+            it += 1
+            break
+        if scheduler is not None and it % st["lr_change_rate"] == 0 and it != 0 and lr_now >= st["lr_min"]:   # :335-338
+            scheduler.step()
+        it += 1
+    return it
 
 
 def main():
@@ -335,69 +396,25 @@ def main():
     TB = int(config["model"]["args"]["TB"])
     out_dir = os.path.join(tr.get("output_path", "./output"), "models", config.get("experiment", "Ours"), args.runid)
 
-    # throughput is counted from the end of the first iteration after which the engine is in its steady state (the first ones
-    # pay module load, allocator growth, the just-in-time calibration of the fp16 operand scales and, with --graph, the
-    # capture: Engine.settled): what is logged is the steady-state rate, whole job (all ranks)
-    t0, frames, it = None, 0, start
     make = synthetic_batch_from_raw_events if args.raw_events else synthetic_batch
     real = real_data_passes(args.data, config, B, TB, device, rank, world, args.seed, args.loader, args.prefetch) if args.data else None
-    valid_stamp, valid_batches, tracker = 1, None, None
+    valid_batches, tracker = None, None
     if vs["do_validation"]:
         from ebfi_amd.metrics import MetricTracker
         valid_batches = validation_batches(vs, config, args, B, H, W, TB, device, rank, world)
         tracker = MetricTracker(eng.VALID_KEYS)
-    while it < st["iterations"]:
-        for micro in range(st["accu_step"]):
-            if real is not None:
-                # one pass per latent frame of the loaded periods, in the reference's order (train_ours.py:226-251)
-                batch = next(real)
-            else:
-                # one fresh synthetic batch per pass, different on every rank (seed + rank, like the reference); drawn by the
-                # device generator unless --host-data: the host draw alone would cap the loop at ~15 frames/s
-                batch = make(B, H, W, TB, device=device, seed=args.seed + 1000 * (it * st["accu_step"] + micro), rank=rank,
-                             on_device=not args.host_data)
-            loss = eng.train_step(*batch)
-            if t0 is not None:
-                frames += B * world
-        log_now = it % st["log_step"] == 0 or it == st["iterations"] - 1
-        if log_now:                      # the loss all-reduce is for logging only (train_ours.py:278-279): do it when logging
-            loss = reduce_tensor(loss.clone())
-        lr_now = scheduler.get_last_lr()[0] if scheduler is not None else eng.optimizer.param_groups[0]["lr"]
-        if rank == 0 and log_now:
-            torch.cuda.synchronize()
-            rate = frames / (time.perf_counter() - t0) if t0 is not None and frames else float("nan")
-            print("Iteration: %d/%d train_loss: %.4e learning rate: %.4e  %.1f frames/s"
-                  % (it, st["iterations"], loss.item(), lr_now, rate), flush=True)
-        if t0 is None and eng.settled:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-        # validation every valid_step-th iteration, never at 0 (train_ours.py:309-328); all ranks take part and decide alike
-        best = stop = False
-        if vs["do_validation"] and it % vs["valid_step"] == 0 and it != 0:
-            t_valid = time.perf_counter()
-            val_log = run_validation(eng, valid_batches, tracker, valid_stamp, vs["valid_log_step"], rank)
-            if t0 is not None:           # (the logged rate is the training rate: the stamp's time is taken off the clock)
-                t0 += time.perf_counter() - t_valid
-            stop, best = monitor.evaluate(val_log)
-            if rank == 0:
-                print("Valid stamp: %d %s (best %r)" % (valid_stamp, " ".join("%s: %.6e" % (k, val_log[k]) for k in eng.VALID_KEYS),
-                                                        monitor.best), flush=True)
-                if stop:
-                    print(monitor.stop_message(), flush=True)
-            valid_stamp += 1
-        # periodic checkpoints as train_ours.py:331-333 (saved BEFORE this iteration's scheduler step, like there; also when this
-        # stamp is the best so far, then twice: :665-671), plus one after the last iteration -- the one an early stop ends at too
-        if rank == 0 and ((st["save_period"] and it % st["save_period"] == 0 and it != 0) or best or stop
-                          or it == st["iterations"] - 1):
-            path = os.path.join(out_dir, "checkpoint-iteration%d.pth" % it)
-            for p in save_checkpoint(path, eng, scheduler, config, it, monitor.best if monitor is not None else None, best):
-                print("saved", p, flush=True)
-        if stop:
-            it += 1
-            break
-        if scheduler is not None and it % st["lr_change_rate"] == 0 and it != 0 and lr_now >= st["lr_min"]:   # :335-338
-            scheduler.step()
-        it += 1
+
+    def next_micro_batch(it, micro):
+        if real is not None:
+            # one pass per latent frame of the loaded periods, in the reference's order (train_ours.py:226-251)
+            return next(real)
+        # one fresh synthetic batch per pass, different on every rank (seed + rank, like the reference); drawn by the
+        # device generator unless --host-data: the host draw alone would cap the loop at ~15 frames/s
+        return make(B, H, W, TB, device=device, seed=args.seed + 1000 * (it * st["accu_step"] + micro), rank=rank,
+                    on_device=not args.host_data)
+
+    it = train_loop(eng, next_micro_batch, B, "frames", st, vs, scheduler, monitor, valid_batches, tracker, out_dir, config, rank,
+                    world, start)
     if real is not None:
         real.close()                     # (joins the loader's worker thread)
     if rank == 0 and eng.book is not None:

@@ -10,7 +10,7 @@ model_best_until_iteration{it}.pth; `states` is what ExposureDecision.load_pretr
 The iteration body follows the reference: every period of a load is one micro-step -- blur-level map (model.BlurryFashion) ->
 ExposureDecision -> MSELoss(Ex, ExposureDuty) / accu_step -> backward -- and every accu_step-th micro-step takes the Adam step,
 logs, validates (valid_loss = the reference's sum over a load's periods of MSELoss; valid_mae beside it), saves, then steps the
-lr scheduler.  Settings, scheduler, monitor / early stop, checkpoints and resume are train_ours.py's own helpers; the engine is
+lr scheduler.  That loop, settings, scheduler, monitor / early stop, checkpoints and resume are train_ours.py's own; the engine is
 ebfi_amd.exposure_engine.ExposureEngine.  Data: synthetic batches or, with --data, recorded clips through ebfi_amd.clipdata.
 TensorBoard and image dumps of the reference are out of scope.
 
@@ -20,7 +20,6 @@ TensorBoard and image dumps of the reference are out of scope.
 import argparse
 import os
 import sys
-import time
 
 import torch
 import torch.distributed as dist
@@ -30,9 +29,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 from train_ours import (CHECKPOINT_KEYS, TRAINING_MODE, Monitor, add_loader_arguments, best_checkpoint_name,  # noqa: E402,F401
-                        build_lr_scheduler, checkpoint_state, init_distributed_mode, resume_checkpoint, run_validation, save_checkpoint,
-                        trainer_settings, validation_seeds, validation_settings)
-from ebfi_amd.dp import reduce_tensor  # noqa: E402
+                        build_lr_scheduler, checkpoint_state, clip_dataset, init_distributed_mode, resume_checkpoint, save_checkpoint,
+                        train_loop, trainer_settings, validation_seeds, validation_settings)
 from ebfi_amd.exposure_engine import (BLURRY_FASHIONS, check_fashion, check_model_name,  # noqa: E402,F401
                                       synthetic_exposure_batch)
 
@@ -88,21 +86,12 @@ def exposure_settings(config):
             "height": int(tr.get("height", 128)), "width": int(tr.get("width", 128))}
 
 
-def _clip_dataset(path, ds_cfg, es, device, seed, loader):
-    from ebfi_amd import clipdata
-    return clipdata.ClipDataset(path, time_bins=int(ds_cfg.get("time_bins", es["TB"])),
-                                frames_per_period=int(ds_cfg.get("NumFramePerPeriod", 16)),
-                                frames_per_blurry=int(ds_cfg.get("NumFramePerBlurry", 16)),
-                                exposure_method=ds_cfg.get("ExposureMethod", "Custom"),
-                                exposure_time=ds_cfg.get("ExposureTime", DEFAULT_EXPOSURE_TIME),
-                                device=device, seed=seed, frames=loader, **clipdata.dataset_args_from_config(ds_cfg))
-
-
 def real_data_periods(path, config, es, device, rank, world, seed, loader="device", prefetch=1):
     """Endless stream of (Frame [B,3,H,W], Event [B,TB,2,H,W], Duty [B,1]) micro-steps from recorded clips: one per period of
     every load of a collated batch, in the reference's order (:221-231)."""
     from ebfi_amd import clipdata
-    ds = _clip_dataset(path, (config.get("train_dataloader") or {}).get("dataset") or {}, es, device, seed)
+    ds = clip_dataset(path, (config.get("train_dataloader") or {}).get("dataset") or {}, es["TB"], DEFAULT_EXPOSURE_TIME, device, seed,
+                      loader)
     B = es["batch_size"]
     if len(ds) < B * world:
         raise SystemExit("--data: %d periods in %s, need at least batch_size x world = %d" % (len(ds), path, B * world))
@@ -119,7 +108,7 @@ def validation_batches(vs, es, args, device, rank, world):
     from ebfi_amd import clipdata
     vb = vs["batch_size"] or es["batch_size"]
     if vs["valid_data"]:
-        ds = _clip_dataset(vs["valid_data"], vs["dataset"], es, device, args.seed, args.loader)
+        ds = clip_dataset(vs["valid_data"], vs["dataset"], es["TB"], DEFAULT_EXPOSURE_TIME, device, args.seed, args.loader)
         if len(ds) == 0:
             raise SystemExit("--valid-data: no complete period in %s" % vs["valid_data"])
         return lambda: clipdata.eval_batches(ds, vb, rank=rank, world=world, seed=args.seed, drop_last=vs["drop_last"],
@@ -160,58 +149,20 @@ def main(argv=None):
     out_dir = os.path.join(tr.get("output_path", "./output"), "models", config.get("experiment", "ExposurePretrain"), runid)
 
     real = real_data_periods(args.data, config, es, device, rank, world, args.seed, args.loader, args.prefetch) if args.data else None
-    valid_stamp, valid_batches, tracker = 1, None, None
+    valid_batches, tracker = None, None
     if vs["do_validation"]:
         valid_batches = validation_batches(vs, es, args, device, rank, world)
         tracker = MetricTracker(eng.VALID_KEYS)
-    t0, samples, it = None, 0, start
-    while it < st["iterations"]:
-        for micro in range(st["accu_step"]):
-            if real is not None:
-                batch = next(real)
-            else:
-                batch = synthetic_exposure_batch(B, H, W, TB, es["exposure_time"], es["frames_per_period"], device=device,
-                                                 seed=args.seed + 1000 * (it * st["accu_step"] + micro), rank=rank,
-                                                 on_device=not args.host_data)
-            loss = eng.train_step(*batch)
-            if t0 is not None:
-                samples += B * world
-        log_now = it % st["log_step"] == 0 or it == st["iterations"] - 1
-        if log_now:                      # the loss all-reduce is for logging only (:260-261)
-            loss = reduce_tensor(loss.clone())
-        lr_now = scheduler.get_last_lr()[0] if scheduler is not None else eng.optimizer.param_groups[0]["lr"]
-        if rank == 0 and log_now:
-            torch.cuda.synchronize()
-            rate = samples / (time.perf_counter() - t0) if t0 is not None and samples else float("nan")
-            print("Iteration: %d/%d train_loss: %.4e learning rate: %.4e  %.1f samples/s"
-                  % (it, st["iterations"], loss.item(), lr_now, rate), flush=True)
-        if t0 is None and eng.settled:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-        best = stop = False
-        if vs["do_validation"] and it % vs["valid_step"] == 0 and it != 0:          # :287-304
-            t_valid = time.perf_counter()
-            val_log = run_validation(eng, valid_batches, tracker, valid_stamp, vs["valid_log_step"], rank)
-            if t0 is not None:
-                t0 += time.perf_counter() - t_valid
-            stop, best = monitor.evaluate(val_log)
-            if rank == 0:
-                print("Valid stamp: %d %s (best %r)" % (valid_stamp, " ".join("%s: %.6e" % (k, val_log[k]) for k in eng.VALID_KEYS),
-                                                        monitor.best), flush=True)
-                if stop:
-                    print(monitor.stop_message(), flush=True)
-            valid_stamp += 1
-        if rank == 0 and ((st["save_period"] and it % st["save_period"] == 0 and it != 0) or best or stop
-                          or it == st["iterations"] - 1):
-            path = os.path.join(out_dir, "checkpoint-iteration%d.pth" % it)
-            for p in save_checkpoint(path, eng, scheduler, config, it, monitor.best if monitor is not None else None, best):
-                print("saved", p, flush=True)
-        if stop:
-            it += 1
-            break
-        if scheduler is not None and it % st["lr_change_rate"] == 0 and it != 0 and lr_now >= st["lr_min"]:   # :311-314
-            scheduler.step()
-        it += 1
+
+    def next_micro_batch(it, micro):
+        if real is not None:
+            return next(real)
+        return synthetic_exposure_batch(B, H, W, TB, es["exposure_time"], es["frames_per_period"], device=device,
+                                        seed=args.seed + 1000 * (it * st["accu_step"] + micro), rank=rank,
+                                        on_device=not args.host_data)
+
+    train_loop(eng, next_micro_batch, B, "samples", st, vs, scheduler, monitor, valid_batches, tracker, out_dir, config, rank, world,
+               start)
     if real is not None:
         real.close()                     # (joins the loader's worker thread)
     if world > 1:

@@ -164,6 +164,42 @@ def test_unknown_fashion_and_no_events_model_raise():
         ExposureEngine(device="cpu", precision="bf16")
 
 
+def test_both_trainers_build_recorded_clips_through_one_function_and_the_loader_arrives(tmp_path):
+    """train_ours.clip_dataset is the dataset call of both trainers: every dataset section that reaches it (stage 1's train and
+    valid_dataloader sections, stage 2's) gives a dataset on the asked-for loader, absent keys take the calling script's
+    defaults, and real_data_periods hands its `loader` through (it once did not: --data died before the first step).  Drawing an
+    item needs the device: tests/test_gpu_exposure.py::test_entry_point_trains_on_recorded_clips_with_both_loaders."""
+    import inspect
+    import re
+    import train_ours
+    from ebfi_amd import clipdata
+    entry = _entry()
+    assert entry.clip_dataset is train_ours.clip_dataset
+    clipdata.write_synthetic_clip(str(tmp_path / "clip0.npz"))          # 33 frames of 64 x 64: two periods of 16
+    cfg1, cfg2 = yaml.safe_load(open(CONFIG)), yaml.safe_load(open(os.path.join(os.path.dirname(CONFIG), "train_ours.yml")))
+    es = entry.exposure_settings(cfg1)
+    stage1, stage2 = (es["TB"], entry.DEFAULT_EXPOSURE_TIME), (int(cfg2["model"]["args"]["TB"]), train_ours.DEFAULT_EXPOSURE_TIME)
+    assert stage1 == (16, list(range(1, 16))) and stage2 == (16, [9, 10, 11, 12, 13, 14, 15])
+    sections = {"stage 1 train": (cfg1["train_dataloader"]["dataset"], stage1, [1 / 16, 2 / 16]),
+                "stage 1 valid": (entry.validation_settings(cfg1)["dataset"], stage1, [1 / 16, 2 / 16]),
+                "stage 1 no keys": ({}, stage1, [1 / 16, 2 / 16]),
+                "stage 2 train": ((cfg2.get("train_dataloader") or {}).get("dataset") or {}, stage2, [9 / 16, 10 / 16]),
+                "stage 2 valid": (train_ours.validation_settings(cfg2)["dataset"], stage2, [9 / 16, 10 / 16])}
+    for tag, (ds_cfg, (tb, times), duties) in sections.items():
+        ds = train_ours.clip_dataset(str(tmp_path), ds_cfg, tb, times, "cpu", 123, "host")
+        assert ds.frames == "host" and len(ds) == 2 and ds.time_bins == 16 and ds.device.type == "cpu", tag
+        assert [item[2] for _, item in ds.items] == duties, tag
+    with pytest.raises(ValueError, match="frames must be"):
+        train_ours.clip_dataset(str(tmp_path), {}, 16, [9], "cpu", 123, "pinned")
+    # the one ClipDataset( of the two scripts, and every caller passes its loader on
+    sources = {m: inspect.getsource(m) for m in (train_ours, entry)}
+    assert sum(src.count("ClipDataset(") for src in sources.values()) == 1
+    for fn, loader in ((entry.real_data_periods, "loader"), (entry.validation_batches, "args.loader"),
+                       (train_ours.real_data_passes, "loader"), (train_ours.validation_batches, "args.loader")):
+        calls = re.findall(r"clip_dataset\((.*?)\)\n", inspect.getsource(fn), flags=re.S)
+        assert len(calls) == 1 and calls[0].split(",")[-1].strip() == loader, (fn.__name__, calls)
+
+
 def test_synthetic_exposure_batch_host_draw():
     from ebfi_amd.exposure_engine import synthetic_exposure_batch
     frame, event, duty = synthetic_exposure_batch(5, 8, 12, TB=4, exposure_time=[9, 12, 15], num_frame_per_period=16,

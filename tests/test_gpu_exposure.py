@@ -3,6 +3,7 @@ tests/test_exposure_host.py, the blur-level inputs and one ExposureEngine step a
 accumulation, the loss sequence against a CPU Adam restatement, validation, and the entry point with its hand-over to stage 2."""
 import functools
 import os
+import re
 import subprocess
 import sys
 
@@ -371,3 +372,30 @@ def test_entry_point_writes_checkpoints_resumes_and_feeds_stage2(tmp_path):
     ex1 = eng.predict(frame, event)
     assert ex1.shape == (2, 1) and torch.equal(ex1, ex2)
     assert ((ex1 - 0.5).abs() > 0).any()
+
+
+def test_entry_point_trains_on_recorded_clips_with_both_loaders(tmp_path):
+    """--data / --valid-data on one synthetic clip: trains, validates, and --loader reaches the dataset -- the two loaders are
+    bit-identical (tests/test_gpu_clip_loader.py), so both runs print the same losses."""
+    from ebfi_amd import clipdata
+    clips = tmp_path / "clips"
+    clips.mkdir()
+    clipdata.write_synthetic_clip(str(clips / "clip0.npz"), num_imgs=33, H=64, W=64)
+    cfg = yaml.safe_load(open(CONFIG))
+    cfg["trainer"].update(output_path=str(tmp_path / "out"), do_validation=True, batch_size=2)
+    cfg["trainer"]["iteration_based_train"].update(iterations=4, valid_step=2, train_log_step=1)
+    for section in (cfg["train_dataloader"], cfg["valid_dataloader"]):
+        section["dataset"]["NumFramePerPeriod"] = 8              # four periods; their exposures 1..4 of the shipped list fit
+        crops = section["dataset"]["data_augment"]
+        crops["random_crop"].update(enabled=True, size=[32, 32])
+        crops["center_crop"].update(enabled=False)
+    cfg_path = str(tmp_path / "stage1.yml")
+    yaml.safe_dump(cfg, open(cfg_path, "w"))
+    common = ["-c", cfg_path, "-seed", "5", "--precision", "fp32", "--data", str(clips), "--valid-data", str(clips)]
+    outs = [_child(common + ["-id", "dev"], str(tmp_path)), _child(common + ["-id", "host", "--loader", "host", "--prefetch", "0"], str(tmp_path))]
+    losses = []
+    for out in outs:
+        assert "Iteration: 3/4" in out and "Valid stamp: 1" in out, out[-2000:]
+        losses.append(re.findall(r"(?:train_loss|valid_loss): (\S+)", out))
+        assert len(losses[-1]) >= 5, out[-2000:]                  # four training lines and at least one validation figure
+    assert losses[0] == losses[1], losses
