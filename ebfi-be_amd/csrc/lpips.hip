@@ -20,20 +20,19 @@
 //   distance kernel  one thread per pixel of one layer of one pair: the two channel norms, then sum_c w_c (u0 - u1)^2 (two
 //                    passes over the channels: the difference is formed before it is squared); per-tile fp64 sums
 //   finalize kernel  one wave per pair: fixed-order fp64 sums of each layer's tiles, / (H_l W_l); NaN when a flag is set.
-#include "common.hpp"
+// The finalize kernel, the block sums and the flags' geometry are shared with the VGG-16 trunk: lpips_common.hpp.
+#include "lpips_common.hpp"
 
 #include <cmath>
 
 using namespace ebfi;
+using namespace ebfi::lpips_shared;
 
 namespace {
 
-constexpr int LP_THREADS = 256;
 constexpr int LP_BM = 64;      // output channels of a workgroup
 constexpr int LP_BP = 256;     // output pixels of a workgroup (one per thread in the gather)
 constexpr int LP_BK = 16;      // K chunk
-constexpr int LP_FROWS = 16;   // input rows per finite-check flag
-constexpr int LP_LAYERS = 5;
 constexpr int LP_PAD = 32;     // LDS row padding: the two lane halves of an MFMA operand read land on different banks
 
 constexpr int LP_COUT[LP_LAYERS] = {64, 192, 384, 256, 256};
@@ -84,8 +83,6 @@ struct WsLayout {
     int strips;
 };
 
-int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
-
 WsLayout ws_layout(int64_t N, int C, int H, int W) {
     WsLayout w;
     const Shapes s = shapes(H, W);
@@ -106,23 +103,12 @@ WsLayout ws_layout(int64_t N, int C, int H, int W) {
     return w;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // ------------------------------------------------------------------ parameter packing
 __global__ void pack_weight_kernel(const float *__restrict__ w, int K, int Kpad, int Cout, float *__restrict__ dst) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)Kpad * Cout) return;
     const int k = (int)(i / Cout), co = (int)(i - (int64_t)k * Cout);
     dst[i] = k < K ? w[(int64_t)co * K + k] : 0.f;
-}
-
-__global__ void copy_kernel(const float *__restrict__ src, int n, float *__restrict__ dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[i];
 }
 
 // ------------------------------------------------------------------ non-finite inputs
@@ -162,9 +148,6 @@ struct ConvArgs {
     const float *w, *bias;         // packed [Kpad][Cout], [Cout]
     float *out;                    // [2N][Cout][Ho][Wo]
 };
-
-// torch max_pool2d propagates NaN: a NaN element wins
-__device__ __forceinline__ float nanmax(float m, float v) { return (v > m || v != v) ? v : m; }
 
 // conv1 (11x11, stride 4, padding 2): each thread gathers the K chunk of its own pixel from pred / target
 __global__ __launch_bounds__(LP_THREADS) void lpips_conv1_kernel(ConvArgs a) {
@@ -425,39 +408,8 @@ __global__ __launch_bounds__(LP_THREADS) void distance_kernel(DistArgs a) {
         default: d = pixel_distance<256>(f0, f1, a.head[l], hw); break;
         }
     }
-    double s = wave_sum((double)d);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) a.partial[(int64_t)n * a.tile0[LP_LAYERS] + t] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-struct FinalArgs {
-    const double *partial;
-    const int *flags;
-    int tile0[LP_LAYERS + 1];
-    int hw[LP_LAYERS];
-    int N, nflags;        // flags per image (C * strips)
-    float *lpips, *layers;
-};
-
-__global__ __launch_bounds__(64) void finalize_kernel(FinalArgs a) {
-    const int n = blockIdx.x, lane = threadIdx.x;
-    const double *p = a.partial + (int64_t)n * a.tile0[LP_LAYERS];
-    int bad = 0;
-    for (int i = lane; i < a.nflags; i += 64)
-        bad |= a.flags[(int64_t)n * a.nflags + i] | a.flags[(int64_t)(a.N + n) * a.nflags + i];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bad |= __shfl_xor(bad, d, 64);
-    const float qnan = __builtin_nanf("");
-    double total = 0.0;
-    for (int l = 0; l < LP_LAYERS; ++l) {
-        double s = 0.0;
-        for (int t = a.tile0[l] + lane; t < a.tile0[l + 1]; t += 64) s += p[t];
-        s = wave_sum(s) / (double)a.hw[l];
-        total += s;
-        if (a.layers && lane == 0) a.layers[(int64_t)n * LP_LAYERS + l] = bad ? qnan : (float)s;
-    }
-    if (lane == 0) a.lpips[n] = bad ? qnan : (float)total;
+    const double s = block_sum((double)d, red);
+    if (threadIdx.x == 0) a.partial[(int64_t)n * a.tile0[LP_LAYERS] + t] = s;
 }
 
 }  // namespace

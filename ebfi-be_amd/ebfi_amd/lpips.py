@@ -7,6 +7,10 @@ linear heads ``loss/PerceptualSimilarity/models/weights/v0.1/alex.pth`` and torc
 returned object on an [N, C, H, W] fp32 pair (C in {1, 3}; H, W >= 31) runs ``ebfi_lpips_alex`` -- the AlexNet trunk as
 implicit-GEMM convolutions on fp32 MFMA, then the normalised, head-weighted distances, all on the current stream with no host
 synchronisation -- and returns the float32 device tensor lpips [N].  Definition: include/ebfi_hip.h.
+
+``load_vgg_lpips(lin_path, backbone_path, device)`` is the VGG-16 variant (perceptual_loss(net='vgg')): the heads
+``.../weights/v0.1/vgg.pth`` and torchvision's ``vgg16-397923af.pth``; H, W >= 16; ``ebfi_lpips_vgg`` runs the 13 convolutions on
+the library's exact-fp32 3x3 forward and one tap kernel per layer.  ``load_lpips(net, ...)`` dispatches over 'alex' and 'vgg'.
 """
 import torch
 
@@ -119,3 +123,129 @@ def load_alex_lpips(lin_path, backbone_path, device="cuda", net=NET):
         raise NotImplementedError("LPIPS net=%r is not implemented: only 'alex' has device kernels here (the reference also "
                                   "offers 'vgg' and 'squeeze')" % (net,))
     return AlexLPIPS(*read_alex_weights(lin_path, backbone_path), device)
+
+
+# ------------------------------------------------------------------ the VGG-16 variant
+VGG_CONV_KEYS = tuple("features.%d" % i for i in (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28))
+VGG_CHANNELS = (3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
+VGG_CONV_SHAPES = tuple((VGG_CHANNELS[i + 1], VGG_CHANNELS[i], 3, 3) for i in range(13))
+VGG_HEAD_CHANNELS = (64, 128, 256, 512, 512)     # conv1_2, conv2_2, conv3_3, conv4_3, conv5_3
+VGG_MIN_SIZE = 16                                # four floor-mode 2x2 pools must leave a pixel
+VGG_WORKSPACE_BUDGET = 2 << 30                   # bytes: N is scored in chunks whose workspace stays under it
+
+
+def read_vgg_weights(lin_path, backbone_path):
+    """The 13 conv weights, 13 biases and 5 head vectors as CPU float32 tensors, from the reference's v0.1 vgg.pth and a
+    torchvision VGG-16 state dict (classifier.* is ignored).  A missing or mis-shaped key raises, naming it."""
+    lin = _state_dict(lin_path, "the LPIPS linear heads")
+    trunk = _state_dict(backbone_path, "the VGG-16 trunk")
+    ws = [_take(trunk, key + ".weight", shape, backbone_path) for key, shape in zip(VGG_CONV_KEYS, VGG_CONV_SHAPES)]
+    bs = [_take(trunk, key + ".bias", shape[:1], backbone_path) for key, shape in zip(VGG_CONV_KEYS, VGG_CONV_SHAPES)]
+    hs = [_take(lin, lkey, (1, c, 1, 1), lin_path).reshape(-1) for lkey, c in zip(LIN_KEYS, VGG_HEAD_CHANNELS)]
+    return ws, bs, hs
+
+
+class VggLPIPS:
+    """LPIPS v0.1 with the VGG-16 trunk; parameters packed once on `device`.  The call contract of AlexLPIPS."""
+
+    NET = "vgg"
+    MIN_SIZE = VGG_MIN_SIZE
+
+    def __init__(self, conv_w, conv_b, lin_w, device):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise NotImplementedError("LPIPS runs on an MI355X through libebfi_hip.so only (got device %s)" % self.device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if len(conv_w) != 13 or len(conv_b) != 13 or len(lin_w) != 5:
+            raise ValueError("VggLPIPS takes 13 conv weights, 13 biases and 5 heads, got %d / %d / %d"
+                             % (len(conv_w), len(conv_b), len(lin_w)))
+        h = N.lib()
+        ws = [w.to(self.device, torch.float32).contiguous() for w in conv_w]
+        bs = [b.to(self.device, torch.float32).contiguous() for b in conv_b]
+        hs = [v.to(self.device, torch.float32).contiguous() for v in lin_w]
+        for got, want in zip(ws, VGG_CONV_SHAPES):
+            if tuple(got.shape) != want:
+                raise ValueError("VggLPIPS: a conv weight of shape %s, expected %s" % (tuple(got.shape), want))
+        nbytes = h.ebfi_lpips_vgg_params_bytes()
+        self.params = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+        arr = lambda ts: (N._vp * len(ts))(*[t.data_ptr() for t in ts])   # noqa: E731
+        with torch.cuda.device_of(self.params):
+            rc = h.ebfi_lpips_vgg_pack_params(arr(ws), arr(bs), arr(hs), N.ptr(self.params), nbytes, N.stream_ptr(self.device))
+        N.check(rc, "ebfi_lpips_vgg_pack_params")
+        self._keep = (ws, bs, hs)      # (the pack kernels read them on the stream)
+        self._workspaces = {}
+        self.chunk = None              # pairs per call of the entry point; None: as many as VGG_WORKSPACE_BUDGET holds
+
+    def _chunk(self, n, c, hgt, wid):
+        """Pairs scored per call: every pair's result is independent of its neighbours, so the split changes no bit."""
+        if self.chunk is not None:
+            return max(1, int(self.chunk))
+        per_pair = N.lib().ebfi_lpips_vgg_workspace(1, c, hgt, wid)
+        return max(1, min(n, VGG_WORKSPACE_BUDGET // max(per_pair, 1)))
+
+    def _workspace(self, stream, shape):
+        key = (stream, shape)
+        ws = self._workspaces.get(key)
+        if ws is None:
+            self._workspaces.clear()   # (keep only the latest shape)
+            nbytes = N.lib().ebfi_lpips_vgg_workspace(*shape)
+            if nbytes <= 0:
+                raise ValueError("LPIPS (VGG-16): ebfi_lpips_vgg refuses the shape %s" % (shape,))
+            ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=self.device)
+            self._workspaces[key] = ws
+        return ws
+
+    @torch.no_grad()
+    def __call__(self, pred, target, normalize=True, per_layer=False):
+        """lpips [N] (float32, on the device) of pred vs target [N, C, H, W], C in {1, 3}: normalize=True takes [0, 1]
+        images, False [-1, 1] ones.  per_layer=True also returns the [N, 5] layer terms.  Strided views with unit column
+        stride are read in place."""
+        N.require_gpu(pred, target)
+        if pred.dim() != 4 or pred.shape != target.shape:
+            raise ValueError("LPIPS takes two [N, C, H, W] tensors of one shape, got %s and %s"
+                             % (tuple(pred.shape), tuple(target.shape)))
+        if pred.dtype != torch.float32 or target.dtype != torch.float32:
+            raise ValueError("LPIPS takes float32 tensors, got %s / %s" % (pred.dtype, target.dtype))
+        if pred.device != self.device or target.device != self.device:
+            raise ValueError("pred on %s, target on %s, weights on %s" % (pred.device, target.device, self.device))
+        n, c, hgt, wid = (int(v) for v in pred.shape)
+        if c not in (1, 3):
+            raise ValueError("LPIPS takes 1 or 3 channels, got %d (loss.perceptual_loss averages other counts per channel)" % c)
+        if hgt < VGG_MIN_SIZE or wid < VGG_MIN_SIZE:
+            raise ValueError("LPIPS (VGG-16) needs H, W >= %d, got %d x %d" % (VGG_MIN_SIZE, hgt, wid))
+        pred = pred if pred.stride(3) == 1 else pred.contiguous()
+        target = target if target.stride(3) == 1 else target.contiguous()
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        layers = torch.empty(n, 5, dtype=torch.float32, device=self.device) if per_layer else None
+        if n:
+            step = self._chunk(n, c, hgt, wid)
+            with torch.cuda.device_of(pred):
+                stream = N.stream_ptr(self.device)
+                ws = self._workspace(stream.value, (min(step, n), c, hgt, wid))
+                for i in range(0, n, step):
+                    m = min(step, n - i)
+                    p, t = pred[i:i + m], target[i:i + m]
+                    rc = N.lib().ebfi_lpips_vgg(N.ptr(p), N.i64x4(p.stride()), N.ptr(t), N.i64x4(t.stride()), m, c, hgt, wid,
+                                                1 if normalize else 0, N.ptr(self.params), N.ptr(ws), ws.numel() * 8,
+                                                N.ptr(out[i:i + m]), N.ptr(layers[i:i + m]) if per_layer else None, stream)
+                    N.check(rc, "ebfi_lpips_vgg")
+        return (out, layers) if per_layer else out
+
+
+def load_vgg_lpips(lin_path, backbone_path, device="cuda"):
+    """VggLPIPS from the reference's v0.1 heads (lin_path: vgg.pth) and a torchvision VGG-16 state dict (backbone_path)."""
+    return VggLPIPS(*read_vgg_weights(lin_path, backbone_path), device)
+
+
+NETS = ("alex", "vgg")
+
+
+def load_lpips(net, lin_path, backbone_path, device="cuda"):
+    """The LPIPS model of `net`: 'alex' or 'vgg'.  'squeeze', the reference's third choice, has no device kernels here."""
+    if net == "alex":
+        return load_alex_lpips(lin_path, backbone_path, device=device)
+    if net == "vgg":
+        return load_vgg_lpips(lin_path, backbone_path, device=device)
+    raise NotImplementedError("LPIPS net=%r is not implemented: 'alex' and 'vgg' have device kernels here (the reference also "
+                              "offers 'squeeze')" % (net,))

@@ -32,7 +32,9 @@ over the shortest list); `restored.npz` also carries `psnr` / `ssim` / `mse` [lo
 reference's fourth metric) is scored too when both of its weight files are named -- `--lpips_lin` the reference's
 loss/PerceptualSimilarity/models/weights/v0.1/alex.pth, `--lpips_backbone` torchvision's AlexNet state dict
 (alexnet-owt-7be5be79.pth) -- by ebfi_amd.lpips on the device, after the timed interval like the others: `lpips` then appears
-in the three yml files and in restored.npz.  Without them the key is left out and stderr says so.
+in the three yml files and in restored.npz.  Without them the key is left out and stderr says so.  `--lpips_net vgg` scores
+the VGG-16 variant instead (the two flags then name v0.1/vgg.pth and torchvision's vgg16-397923af.pth): the yml key stays
+`lpips`, restored.npz gains `lpips_net`, and stderr names the net beside each clip's value.
 
 `--real_blur` (the second block of scripts/infer_ours.sh) reads the clips as exposure-stamped recordings of a real camera
 (ebfi_amd.clipdata.RealBlurClipDataset, the counterpart of dataloader/h5dataset_realdata.py): every stored frame is a blurry
@@ -132,6 +134,9 @@ def get_flags(argv=None):
                          "--lpips_backbone, the metrics also score LPIPS)")
     ap.add_argument("--lpips_backbone", type=str, default=None,
                     help="LPIPS: torchvision's AlexNet state dict (alexnet-owt-7be5be79.pth of the torch hub cache)")
+    ap.add_argument("--lpips_net", type=str, default="alex", choices=("alex", "vgg"),
+                    help="LPIPS: the trunk, the reference's perceptual_loss(net=...).  With vgg, --lpips_lin names v0.1/vgg.pth "
+                         "and --lpips_backbone torchvision's VGG-16 state dict (vgg16-397923af.pth); the yml key stays `lpips`")
     ap.add_argument("--data_seed", type=int, default=123, help="base of the per-item seeds (noise draw); the reference seeds "
                                                                 "python's generator with 123 and draws one seed per item")
     ap.add_argument("--batch", type=int, default=4, help="synthetic mode (no --data_list)")
@@ -252,7 +257,7 @@ def summarise_clips(results, info):
 def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, metrics=True, info="", lpips=None, event_png=False):
     """infer_body of the reference for one clip: every sequence, every load, every latent timestamp; returns
     (frames written, seconds inside the model, (result, result_step) or None without metrics).  lpips: an
-    ebfi_amd.lpips.AlexLPIPS that scores LPIPS as a fourth metric, or None."""
+    ebfi_amd.lpips.AlexLPIPS or VggLPIPS that scores LPIPS as a fourth metric, or None."""
     from ebfi_amd import clipdata
     from ebfi_amd.metrics import MetricTracker, frame_metrics
     name = os.path.basename(data_path)
@@ -272,6 +277,7 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, me
         os.makedirs(os.path.join(img_path, "event"), exist_ok=False)
     restored, blurry, duties, stamps, loads = [], [], [], [], []
     scores = []                                            # per load: [3 (psnr, ssim, mse) or 4 (+ lpips), NumF]
+    lpips_net = getattr(lpips, "NET", "alex")              # (the yml key stays `lpips`, the reference's, whatever the net)
     track = MetricTracker(["mse", "psnr", "ssim"] + (["lpips"] if lpips is not None else []))
     step = {"psnr": []}
     iL = iF = -1
@@ -325,6 +331,8 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, me
             extra = dict(psnr=sc[:, 0], ssim=sc[:, 1], mse=sc[:, 2])
             if lpips is not None:
                 extra["lpips"] = sc[:, 3]
+                if lpips_net != "alex":                    # (an AlexNet run writes what it always wrote)
+                    extra["lpips_net"] = np.array(lpips_net)
         np.savez(os.path.join(root_path, "restored.npz"), restored=np.stack(restored), blurry=np.stack(blurry),
                  exposure_duty=np.array(duties, dtype=np.float32), timestamps=np.stack(stamps), period=np.array(loads), **extra)
     print("%s: %d loads, %d frames restored -> %s" % (name, iL + 1, iF + 1, root_path), flush=True)
@@ -335,6 +343,8 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, me
                                                               "evaluation step results": step})
     print("%s: psnr %.4f  ssim %.4f  mse %.6g over %d frames" % (name, result["psnr"], result["ssim"], result["mse"], iF + 1),
           flush=True)
+    if lpips is not None and lpips_net != "alex":
+        warn("%s: lpips (%s) %.6g over %d frames" % (name, lpips_net, result["lpips"], iF + 1))
     return iF + 1, spent, (result, step)
 
 
@@ -434,8 +444,8 @@ def run_data_list(flags, interp, device):
     metrics = not flags.no_metrics and not flags.real_blur      # (the real_blur note has said that nothing is scored)
     lpips = None
     if metrics and flags.lpips_lin is not None:
-        from ebfi_amd.lpips import load_alex_lpips
-        lpips = load_alex_lpips(flags.lpips_lin, flags.lpips_backbone, device=device)
+        from ebfi_amd.lpips import load_lpips
+        lpips = load_lpips(flags.lpips_net, flags.lpips_lin, flags.lpips_backbone, device=device)
     elif metrics:
         from ebfi_amd.metrics import LPIPS_UNAVAILABLE
         warn(LPIPS_UNAVAILABLE + "; psnr / ssim / mse only")

@@ -21,15 +21,16 @@ class psnr_loss:
 
 
 class perceptual_loss:
-    """LPIPS (AlexNet, v0.1) on the device, from the two weight files named here: lin_path, the reference's
+    """LPIPS (v0.1) on the device, from the two weight files named here: lin_path, the reference's
     loss/PerceptualSimilarity/models/weights/v0.1/alex.pth, and backbone_path, torchvision's AlexNet state dict
-    (alexnet-owt-7be5be79.pth).  Without them it raises: no weight cache is searched."""
+    (alexnet-owt-7be5be79.pth); with net='vgg', v0.1/vgg.pth and torchvision's VGG-16 state dict (vgg16-397923af.pth).
+    Without them it raises: no weight cache is searched.  net='squeeze' is refused."""
 
     def __init__(self, weight=1.0, net='alex', use_gpu=True, gpu_ids=[0], lin_path=None, backbone_path=None):
         if lin_path is None or backbone_path is None:
             raise NotImplementedError(LPIPS_UNAVAILABLE)
-        from ebfi_amd.lpips import load_alex_lpips
-        self.model = load_alex_lpips(lin_path, backbone_path, device="cuda:%d" % gpu_ids[0], net=net)
+        from ebfi_amd.lpips import load_lpips
+        self.model = load_lpips(net, lin_path, backbone_path, device="cuda:%d" % gpu_ids[0])
         self.weight = weight
 
     def __call__(self, pred, target, normalize=True):

@@ -46,6 +46,7 @@
  *                               the Vid2E adaptive upsampler (generate_dataset/upsampling/utils/{upsampler,model}.py)
  *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
  *   ebfi_lpips_*                perceptual_loss(net='alex') of the evaluation loop (loss/restore.py:10-40, LPIPS v0.1)
+ *   ebfi_lpips_vgg*             perceptual_loss(net='vgg'), likewise
  *   ebfi_charbonnier_*          CharbonnierLoss of the validation loop (loss/restore.py:95-105, train_ours.py:588)
  *   ebfi_duty_head_*            tail of ExposureDecision.forward + nn.MSELoss of stage 1 (model_singleframe.py:75-76,
  *                               train_ours_exposuredecision.py:250-252)
@@ -94,7 +95,8 @@ extern "C" {
  *      ebfi_period_frames_u8 (the sharp frames and the exposure mean of a training period from its stored bytes), likewise; and
  *      ebfi_esim_loop_bound / _init / _count / _emit (the event simulator of the synthetic-dataset step), likewise; and
  *      ebfi_avgpool2_forward / ebfi_bilinear_up2_forward / ebfi_flow_max_magnitude / ebfi_slomo_assemble / _blend / _frame_u8
- *      (the frame-upsampling step), likewise -- with them ebfi_conv2d_forward accepts ksize 5 at stride 1, which it refused */
+ *      (the frame-upsampling step), likewise -- with them ebfi_conv2d_forward accepts ksize 5 at stride 1, which it refused; and
+ *      ebfi_lpips_vgg_params_bytes / _pack_params / _workspace / ebfi_lpips_vgg (evaluation LPIPS, VGG-16 v0.1), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -698,6 +700,29 @@ int64_t ebfi_lpips_workspace(int64_t N, int C, int H, int W);
 int ebfi_lpips_alex(const float *pred, const int64_t pred_strides[4], const float *target, const int64_t target_strides[4],
                     int64_t N, int C, int H, int W, int normalize, const void *params, void *workspace, int64_t workspace_bytes,
                     float *out_lpips, float *out_layers, void *stream);
+
+/* ------------------------------------------------------------------ evaluation LPIPS (VGG-16, v0.1)
+ * perceptual_loss(net='vgg'): the definition of ebfi_lpips_alex with the trunk exchanged (PNetLin(pnet_type='vgg', version='0.1',
+ * spatial=False) in eval mode).  x', d_l, lpips[n], out_layers, the strides, the NaN / Inf rule and the launch contract are those
+ * above; the zero padding of the first convolution applies to x' (it is not folded into the weights).
+ *   f1 .. f5 = the ReLU outputs of conv1_2, conv2_2, conv3_3, conv4_3, conv5_3 (64, 128, 256, 512, 512 channels) of torchvision's
+ *              vgg16.features: 13 convolutions 3x3 / stride 1 / pad 1 with bias and ReLU, channels
+ *              3-64-64 | 128-128 | 256-256-256 | 512-512-512 | 512-512-512, `|` a 2x2 / stride 2 max-pool without padding in floor
+ *              mode (an odd last row or column is dropped; NaN propagating)
+ * The convolutions are ebfi_conv2d_forward's exact-fp32 3x3 kernel, called inside; each tap map is read by one kernel that
+ * forms the norms and the head-weighted differences in fp64 and writes the pooled map of the next block.
+ * ebfi_lpips_vgg_pack_params takes host arrays of 13 (conv_w [Cout][Cin][3][3], conv_b [Cout], in the order of the keys
+ * features.{0,2,5,7,10,12,14,17,19,21,24,26,28}) and 5 (lin_w) device pointers, fp32 contiguous.  workspace: the scaled inputs,
+ * two maps of the largest layer ([2N][64][H][W] fp32 each: 0.94 GB per 720 x 1280 pair together), tile partials and flags.
+ * H, W >= 16 (four pools must leave a pixel); H * W <= 4063231 and N <= 16384 in one call; ebfi_lpips_vgg_workspace returns 0
+ * for a shape the entry point refuses.  Error codes as ebfi_lpips_alex. */
+int64_t ebfi_lpips_vgg_params_bytes(void);
+int ebfi_lpips_vgg_pack_params(const float *const *conv_w, const float *const *conv_b, const float *const *lin_w, void *params,
+                               int64_t params_bytes, void *stream);
+int64_t ebfi_lpips_vgg_workspace(int64_t N, int C, int H, int W);
+int ebfi_lpips_vgg(const float *pred, const int64_t pred_strides[4], const float *target, const int64_t target_strides[4],
+                   int64_t N, int C, int H, int W, int normalize, const void *params, void *workspace, int64_t workspace_bytes,
+                   float *out_lpips, float *out_layers, void *stream);
 
 /* ------------------------------------------------------------------ Charbonnier loss (validation)
  * CharbonnierLoss of the reference (loss/restore.py:95-105; the validation score of train_ours.py:588) per sample n of an fp32

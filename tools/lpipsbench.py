@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
-"""LPIPS (ebfi_amd.lpips: finite check, five implicit-GEMM convolutions on fp32 MFMA, distance + finalize kernels) at the size of
-one config 5 load -- 16 pairs of 3 x 720 x 1280 -- and at 16 x 3 x 256 x 256: device events around `iters` calls after a
-warm-up, with a random AlexNet trunk (the time does not depend on the weights).  Prints microseconds per call, the algorithmic
-FLOPs of each trunk layer (2 * pixels * Cout * Cin * k * k per image, from the shapes here) and the achieved fraction of the
-157.3 TF fp32 matrix peak.  usage: python tools/lpipsbench.py [iters]"""
+"""LPIPS (ebfi_amd.lpips) timed with device events around `iters` calls after a warm-up, with a random trunk (the time does not
+depend on the weights).  Prints one JSON line per shape: microseconds per call, the algorithmic FLOPs of each trunk layer
+(2 * pixels * Cout * Cin * k * k per image, from the shapes here) and the achieved fraction of the 157.3 TF fp32 matrix peak.
+
+  --net alex (default)  finite check, five implicit-GEMM convolutions on fp32 MFMA, distance + finalize kernels, at the size of
+                        one config 5 load -- 16 pairs of 3 x 720 x 1280 -- and at 16 x 3 x 256 x 256
+  --net vgg             prologue, 13 exact-fp32 3x3 convolutions, five tap kernels, finalize: one 720 x 1280 pair and sixteen
+                        256 x 256 pairs; mean and spread (min / max) over the timed calls, the share of the fp32 matrix bound
+                        (FLOPs / peak: arithmetic from the shapes, not a measurement), per-kernel rows from the library's event
+                        profiler (a separate pass: its events serialise the launches), and the AlexNet figure of the same call
+
+usage: python tools/lpipsbench.py [iters] [--net {alex,vgg}]"""
+import argparse
 import json
 import os
 import sys
@@ -12,10 +20,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ebfi-be_amd"))
 import torch  # noqa: E402
 
-from ebfi_amd.lpips import CONV_SHAPES, AlexLPIPS  # noqa: E402
+from ebfi_amd import _native as N  # noqa: E402
+from ebfi_amd.lpips import CONV_SHAPES, VGG_CONV_SHAPES, VGG_HEAD_CHANNELS, AlexLPIPS, VggLPIPS  # noqa: E402
 
 FP32_MATRIX_PEAK = 157.3e12
-ITERS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 
 
 def layer_flops(n_images, H, W):
@@ -26,34 +34,107 @@ def layer_flops(n_images, H, W):
     return [2.0 * n_images * p * co * ci * k * k for p, (co, ci, k, _) in zip(pixels, CONV_SHAPES)]
 
 
-def bench(model, N, C, H, W):
+def vgg_layer_flops(n_images, H, W):
+    level = [0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4]          # pools before each of the 13 convolutions
+    return [2.0 * n_images * (H >> s) * (W >> s) * co * ci * 9 for s, (co, ci, _, _) in zip(level, VGG_CONV_SHAPES)]
+
+
+def pair(N_, C, H, W):
     g = torch.Generator(device="cuda").manual_seed(0)
-    target = torch.rand(N, C, H, W, device="cuda", generator=g)
-    pred = target + 0.05 * torch.randn(N, C, H, W, device="cuda", generator=g)
+    target = torch.rand(N_, C, H, W, device="cuda", generator=g)
+    pred = target + 0.05 * torch.randn(N_, C, H, W, device="cuda", generator=g)
+    return pred, target
+
+
+def time_calls(model, pred, target, iters):
+    """Per-call microseconds of `iters` calls, each between its own pair of device events."""
+    for _ in range(3):
+        model(pred, target)
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for t0, t1 in ev:
+        t0.record()
+        model(pred, target)
+        t1.record()
+    torch.cuda.synchronize()
+    return [t0.elapsed_time(t1) * 1e3 for t0, t1 in ev]
+
+
+def bench(model, N_, C, H, W, iters):
+    pred, target = pair(N_, C, H, W)
     for _ in range(3):
         model(pred, target)
     torch.cuda.synchronize()
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
-    for _ in range(ITERS):
+    for _ in range(iters):
         model(pred, target)
     t1.record()
     torch.cuda.synchronize()
-    us = t0.elapsed_time(t1) * 1e3 / ITERS
-    fl = layer_flops(2 * N, H, W)
-    row = dict(shape=[N, C, H, W], us_per_call=round(us, 1), us_per_pair=round(us / N, 2),
+    us = t0.elapsed_time(t1) * 1e3 / iters
+    fl = layer_flops(2 * N_, H, W)
+    row = dict(shape=[N_, C, H, W], us_per_call=round(us, 1), us_per_pair=round(us / N_, 2),
                gflop_per_layer=[round(f / 1e9, 2) for f in fl], gflop=round(sum(fl) / 1e9, 1),
                tflops=round(sum(fl) / (us * 1e-6) / 1e12, 2), fp32_matrix_peak_fraction=round(sum(fl) / (us * 1e-6) / FP32_MATRIX_PEAK, 3))
     print(json.dumps(row), flush=True)
     return row
 
 
+def kernel_rows(model, pred, target, iters):
+    """{kernel: microseconds per call} from the library's event profiler."""
+    N.prof_enable(True)
+    N.prof_reset()
+    try:
+        for _ in range(iters):
+            model(pred, target)
+            torch.cuda.synchronize()
+            N.prof_fold()
+        stats = N.prof_collect(strict=False)
+    finally:
+        N.prof_enable(False)
+        N.prof_reset()
+    return {k: dict(launches_per_call=v[0] // iters, us_per_call=round(v[1] * 1e3 / iters, 1),
+                    tflops=round(v[2] / max(v[1] * 1e-3, 1e-12) / 1e12, 2) if v[2] else None,
+                    gbytes_per_s=round(v[3] / max(v[1] * 1e-3, 1e-12) / 1e9, 1) if v[3] else None)
+            for k, v in sorted(stats.items()) if not k.startswith("__") and v[0]}
+
+
+def bench_vgg(vgg, alex, N_, C, H, W, iters):
+    pred, target = pair(N_, C, H, W)
+    us = time_calls(vgg, pred, target, iters)
+    us_alex = time_calls(alex, pred, target, iters)
+    mean = sum(us) / len(us)
+    fl = vgg_layer_flops(2 * N_, H, W)
+    bound_us = sum(fl) / FP32_MATRIX_PEAK * 1e6
+    row = dict(net="vgg", shape=[N_, C, H, W], chunk=vgg._chunk(N_, C, H, W), us_per_call=round(mean, 1), us_min=round(min(us), 1),
+               us_max=round(max(us), 1), us_per_pair=round(mean / N_, 1), gflop_per_conv=[round(f / 1e9, 2) for f in fl],
+               gflop=round(sum(fl) / 1e9, 1), fp32_matrix_bound_us=round(bound_us, 1), tflops=round(sum(fl) / (mean * 1e-6) / 1e12, 2),
+               fp32_matrix_peak_fraction=round(bound_us / mean, 3),
+               alex_us_per_call=round(sum(us_alex) / len(us_alex), 1), alex_us_min=round(min(us_alex), 1),
+               alex_us_max=round(max(us_alex), 1), kernels=kernel_rows(vgg, pred, target, min(iters, 3)))
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def random_weights(shapes, heads, g):
+    ws = [torch.randn(s, generator=g) * (2.0 / (s[1] * s[2] * s[3])) ** 0.5 for s in shapes]
+    bs = [0.01 + 0.05 * torch.rand(s[0], generator=g) for s in shapes]
+    hs = [torch.rand(c, generator=g) for c in heads]
+    return ws, bs, hs
+
+
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("iters", type=int, nargs="?", default=10)
+    ap.add_argument("--net", choices=("alex", "vgg"), default="alex")
+    a = ap.parse_args()
     assert torch.cuda.is_available(), "lpipsbench needs the MI355X"
     g = torch.Generator().manual_seed(0)
-    ws = [torch.randn(s, generator=g) * (2.0 / (s[1] * s[2] * s[3])) ** 0.5 for s in CONV_SHAPES]
-    bs = [0.01 + 0.05 * torch.rand(s[0], generator=g) for s in CONV_SHAPES]
-    hs = [torch.rand(s[0], generator=g) for s in CONV_SHAPES]
-    model = AlexLPIPS(ws, bs, hs, "cuda")
-    bench(model, 16, 3, 720, 1280)
-    bench(model, 16, 3, 256, 256)
+    alex = AlexLPIPS(*random_weights(CONV_SHAPES, [s[0] for s in CONV_SHAPES], g), "cuda")
+    if a.net == "alex":
+        bench(alex, 16, 3, 720, 1280, a.iters)
+        bench(alex, 16, 3, 256, 256, a.iters)
+    else:
+        vgg = VggLPIPS(*random_weights(VGG_CONV_SHAPES, VGG_HEAD_CHANNELS, g), "cuda")
+        bench_vgg(vgg, alex, 1, 3, 720, 1280, a.iters)
+        bench_vgg(vgg, alex, 16, 3, 256, 256, a.iters)
