@@ -148,6 +148,9 @@ SIGNATURES = {
     "ebfi_lpips_vgg_pack_params": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "ebfi_lpips_vgg_workspace": (_i64, [_i64, _i, _i, _i]),
     "ebfi_lpips_vgg": (_i, [_vp, _p64, _vp, _p64, _i64, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ebfi_lpips_vgg_train_workspace": (_i64, [_i64, _i, _i, _i]),
+    "ebfi_lpips_vgg_forward_train": (_i, [_vp, _p64, _vp, _p64, _i64, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ebfi_lpips_vgg_backward": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _p64, _vp]),
     "ebfi_charbonnier_workspace": (_i64, [_i64, _i, _i, _i]),
     "ebfi_charbonnier_forward": (_i, [_vp, _p64, _vp, _p64, _i64, _i, _i, _i, _c.c_float, _vp, _i64, _vp, _vp]),
     "ebfi_charbonnier_backward": (_i, [_vp, _p64, _vp, _p64, _i64, _i, _i, _i, _c.c_float, _vp, _vp, _vp]),

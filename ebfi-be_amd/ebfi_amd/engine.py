@@ -84,9 +84,13 @@ def synthetic_validation_batch(B, H, W, TB=16, num_frames=4, device="cuda", seed
 
 class Engine(graphstep.GraphStepper):
     def __init__(self, model_args=None, device="cuda", precision="fp32", lr=1e-4, seed=None, train=True, graph=False,
-                 accu_step=1, betas=(0.9, 0.999), backward_f16=None, forward_f16="filters", strict_graph=None):
+                 accu_step=1, betas=(0.9, 0.999), backward_f16=None, forward_f16="filters", strict_graph=None,
+                 perceptual=None):
         """graph / accu_step / strict_graph: see graphstep.GraphStepper (a graph is captured per input shape, precision and loss
         phase).
+        perceptual: None, or an ebfi_amd.loss.PerceptualTerm: its value for (Sharp, target), / accu_step, is added to the training
+        loss before the backward pass, inside the captured step.  The LPIPS weights are not model parameters: they are neither
+        trained nor saved.  With None not one launch of the step changes.
         forward_f16 (only with the fp16 backward; ignored otherwise): which FORWARD convolutions read fp16 operand images (one matrix-core product per
         tap, fp32 accumulation) instead of running in split precision:
           "filters"  the 128 -> 1600 KernelConv of Modification, whose output exists only as fp16 planes anyway (ebfi_amd.fac):
@@ -114,6 +118,7 @@ class Engine(graphstep.GraphStepper):
         # moves by lr) lifts them to 1e-4 -- fourteen decades in one step, which no one-step-old scale survives.  From the
         # third step on magnitudes move by a few percent per step and the delayed scales (f16scale) take over.
         self.calibration_steps = 2
+        self.perceptual = perceptual if train else None
         if train:
             self.model.train()
             self.loss = TrainLoss(self.model_args.get("DetailEnabled", True)).to(self.device)
@@ -162,6 +167,8 @@ class Engine(graphstep.GraphStepper):
                 book.calibrated.clear()             # (measure every operand of this pass again, see __init__)
             sharp_pre, sharp = self.model(frame, event, t, gtex)
             loss = self.loss(sharp_pre.float(), sharp.float(), target, self.iteration, self.accu_step)
+            if self.perceptual is not None:
+                loss = loss + self.perceptual(sharp.float(), target) / self.accu_step
             loss.backward()
             if book is not None:
                 book.finish()                       # next step's operand scales from this pass's maxima; guard on overflow

@@ -268,6 +268,23 @@ class TrainLoss(nn.Module):
         return (c_sharp * term(sharp) + c_pre * term(sharp_pre)) / accu_step
 
 
+class PerceptualTerm:
+    """weight * mean over the batch of LPIPS (VGG-16) as a term of the training loss (the reference builds perceptual_loss beside
+    Lap and census, train_ours.py:765): `model` is an ebfi_amd.lpips.VggLPIPS, whose weights are no parameters of the trained
+    model and enter no checkpoint.  term(pred, target) -> 0-dim tensor with a graph into pred; images in [0, 1]."""
+
+    def __init__(self, model, weight):
+        if not hasattr(model, "loss"):
+            raise NotImplementedError("PerceptualTerm needs an LPIPS model with a backward (ebfi_amd.lpips.VggLPIPS); %s is a "
+                                      "score only" % type(model).__name__)
+        if not float(weight) > 0:
+            raise ValueError("PerceptualTerm: the weight must be positive, got %r (leave the term out instead)" % (weight,))
+        self.model, self.weight = model, float(weight)
+
+    def __call__(self, pred, target):
+        return self.weight * self.model.loss(pred, target.detach(), normalize=True).mean()
+
+
 # ------------------------------------------------------------------------------------------------ Charbonnier (validation)
 _cb_workspaces = {}
 

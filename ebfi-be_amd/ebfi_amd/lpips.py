@@ -11,7 +11,16 @@ synchronisation -- and returns the float32 device tensor lpips [N].  Definition:
 ``load_vgg_lpips(lin_path, backbone_path, device)`` is the VGG-16 variant (perceptual_loss(net='vgg')): the heads
 ``.../weights/v0.1/vgg.pth`` and torchvision's ``vgg16-397923af.pth``; H, W >= 16; ``ebfi_lpips_vgg`` runs the 13 convolutions on
 the library's exact-fp32 3x3 forward and one tap kernel per layer.  ``load_lpips(net, ...)`` dispatches over 'alex' and 'vgg'.
+
+``VggLPIPS.loss(pred, target)`` is the same value as a training loss (the reference builds perceptual_loss beside its Laplacian
+and census terms, train_ours.py:765): one autograd node whose forward, ``ebfi_lpips_vgg_forward_train``, keeps the 13 ReLU maps of
+the pred images and the 5 tap maps of the target images, and whose backward, ``ebfi_lpips_vgg_backward``, runs one fused tap
+adjoint per layer (distance gradient plus the max-pool's routed gradient) and the 13 data gradients of the library's exact-fp32
+3x3 kernel.  pred gets the gradient, the target none.  The AlexNet trunk is forward-only: its 11x11 stride-4 and 5x5 layers have
+no data-gradient kernel in the library, so ``AlexLPIPS`` has no ``loss``.
 """
+import weakref
+
 import torch
 
 from . import _native as N
@@ -53,7 +62,8 @@ def read_alex_weights(lin_path, backbone_path):
 
 
 class AlexLPIPS:
-    """LPIPS v0.1 with the AlexNet trunk; parameters packed once on `device`."""
+    """LPIPS v0.1 with the AlexNet trunk; parameters packed once on `device`.  A score only: there is no backward (the 11x11
+    stride-4 and 5x5 layers have no data-gradient kernel in the library); VggLPIPS.loss is the training loss."""
 
     def __init__(self, conv_w, conv_b, lin_w, device):
         self.device = torch.device(device)
@@ -175,6 +185,7 @@ class VggLPIPS:
         N.check(rc, "ebfi_lpips_vgg_pack_params")
         self._keep = (ws, bs, hs)      # (the pack kernels read them on the stream)
         self._workspaces = {}
+        self._train_pool = []
         self.chunk = None              # pairs per call of the entry point; None: as many as VGG_WORKSPACE_BUDGET holds
 
     def _chunk(self, n, c, hgt, wid):
@@ -196,11 +207,8 @@ class VggLPIPS:
             self._workspaces[key] = ws
         return ws
 
-    @torch.no_grad()
-    def __call__(self, pred, target, normalize=True, per_layer=False):
-        """lpips [N] (float32, on the device) of pred vs target [N, C, H, W], C in {1, 3}: normalize=True takes [0, 1]
-        images, False [-1, 1] ones.  per_layer=True also returns the [N, 5] layer terms.  Strided views with unit column
-        stride are read in place."""
+    def _check(self, pred, target):
+        """The pair as the entry points take it (unit column stride), or the error that names what is wrong with it."""
         N.require_gpu(pred, target)
         if pred.dim() != 4 or pred.shape != target.shape:
             raise ValueError("LPIPS takes two [N, C, H, W] tensors of one shape, got %s and %s"
@@ -216,6 +224,69 @@ class VggLPIPS:
             raise ValueError("LPIPS (VGG-16) needs H, W >= %d, got %d x %d" % (VGG_MIN_SIZE, hgt, wid))
         pred = pred if pred.stride(3) == 1 else pred.contiguous()
         target = target if target.stride(3) == 1 else target.contiguous()
+        return pred, target
+
+    def _train_workspace(self, stream, shape):
+        """A training workspace of (stream, shape) that no pending backward still reads.  One is enough for a loss evaluated once
+        per step, and it is then the same buffer in every step; a second forward before the first one's backward --
+        perceptual_loss's per-channel loop -- takes a second buffer.  Buffers of other shapes are dropped.  Inside a stream
+        capture nothing should be allocated, and the capture runs on a stream of its own: it takes a free buffer of the shape
+        whatever stream the eager passes before it left it on (every captured step here runs eagerly first).  A buffer that a
+        captured graph replays on is kept for good and never handed to an eager call."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        self._train_pool = [e for e in self._train_pool if e.shape == shape or e.captured]
+        for entry in self._train_pool:
+            if entry.shape == shape and entry.free() and (capturing or (entry.stream == stream and not entry.captured)):
+                entry.captured = entry.captured or capturing
+                return entry
+        nbytes = N.lib().ebfi_lpips_vgg_train_workspace(*shape)
+        if nbytes <= 0:
+            raise ValueError("LPIPS (VGG-16): ebfi_lpips_vgg_forward_train refuses the shape %s" % (shape,))
+        buf = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=self.device)
+        entry = _TrainWorkspace(buf, stream, shape, capturing)
+        self._train_pool.append(entry)
+        return entry
+
+    def _forward_train(self, pred, target, normalize, entry):
+        n, c, hgt, wid = (int(v) for v in pred.shape)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        with torch.cuda.device_of(pred):
+            rc = N.lib().ebfi_lpips_vgg_forward_train(N.ptr(pred), N.i64x4(pred.stride()), N.ptr(target), N.i64x4(target.stride()), n,
+                                                      c, hgt, wid, 1 if normalize else 0, N.ptr(self.params), N.ptr(entry.buf),
+                                                      entry.buf.numel() * 8, N.ptr(out), None, N.stream_ptr(self.device))
+        N.check(rc, "ebfi_lpips_vgg_forward_train")
+        return out
+
+    def _backward(self, grad_out, shape, normalize, entry):
+        n, c, hgt, wid = shape
+        grad_out = grad_out.to(torch.float32).contiguous()
+        grad_pred = torch.empty(shape, dtype=torch.float32, device=self.device)
+        with torch.cuda.device_of(grad_pred):
+            rc = N.lib().ebfi_lpips_vgg_backward(N.ptr(grad_out), N.ptr(self.params), N.ptr(entry.buf), entry.buf.numel() * 8, n, c,
+                                                 hgt, wid, 1 if normalize else 0, N.ptr(grad_pred), N.i64x4(grad_pred.stride()),
+                                                 N.stream_ptr(self.device))
+        N.check(rc, "ebfi_lpips_vgg_backward")
+        return grad_pred
+
+    def loss(self, pred, target, normalize=True):
+        """lpips [N] of pred vs target as `__call__` returns it, bit for bit, with a graph: its backward is the gradient with
+        respect to pred (ebfi_lpips_vgg_backward: the tap adjoints and the 13 data gradients on the device).  The target gets
+        none, and one that requires grad is refused.  All pairs go through one call: the workspace (ebfi_lpips_vgg_train_workspace)
+        keeps the 13 ReLU maps of the pred images."""
+        if target.requires_grad:
+            raise ValueError("VggLPIPS.loss has no gradient for the target: pass target.detach() (got a target that requires grad)")
+        pred, target = self._check(pred, target)
+        if pred.shape[0] == 0:
+            return pred.new_zeros(0) + 0.0 * pred.sum()
+        return _VggLoss.apply(pred, target, self, bool(normalize))
+
+    @torch.no_grad()
+    def __call__(self, pred, target, normalize=True, per_layer=False):
+        """lpips [N] (float32, on the device) of pred vs target [N, C, H, W], C in {1, 3}: normalize=True takes [0, 1]
+        images, False [-1, 1] ones.  per_layer=True also returns the [N, 5] layer terms.  Strided views with unit column
+        stride are read in place."""
+        pred, target = self._check(pred, target)
+        n, c, hgt, wid = (int(v) for v in pred.shape)
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         layers = torch.empty(n, 5, dtype=torch.float32, device=self.device) if per_layer else None
         if n:
@@ -231,6 +302,51 @@ class VggLPIPS:
                                                 N.ptr(out[i:i + m]), N.ptr(layers[i:i + m]) if per_layer else None, stream)
                     N.check(rc, "ebfi_lpips_vgg")
         return (out, layers) if per_layer else out
+
+
+class _TrainWorkspace:
+    """A training workspace and who reads it: the forward that filled it claims it until its backward has run (or its graph
+    node has been dropped without one)."""
+
+    class _Claim:
+        __slots__ = ("__weakref__",)
+
+    def __init__(self, buf, stream, shape, captured):
+        self.buf, self.stream, self.shape, self.captured = buf, stream, shape, captured
+        self._owner, self.generation = None, 0
+
+    def free(self):
+        return self._owner is None or self._owner() is None
+
+    def claim(self):
+        token = self._Claim()
+        self._owner = weakref.ref(token)
+        self.generation += 1
+        return token, self.generation
+
+    def release(self):
+        self._owner = None
+
+
+class _VggLoss(torch.autograd.Function):
+    """lpips [N] of VggLPIPS.loss: ebfi_lpips_vgg_forward_train and ebfi_lpips_vgg_backward around one workspace."""
+
+    @staticmethod
+    def forward(ctx, pred, target, model, normalize):
+        entry = model._train_workspace(N.stream_ptr(model.device).value, tuple(int(v) for v in pred.shape))
+        out = model._forward_train(pred, target, normalize, entry)
+        ctx.model, ctx.normalize, ctx.entry, ctx.shape = model, normalize, entry, tuple(int(v) for v in pred.shape)
+        ctx.claim, ctx.generation = entry.claim()
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if ctx.entry.generation != ctx.generation:
+            raise RuntimeError("VggLPIPS.loss: a later forward has overwritten the workspace of this one (its backward had "
+                               "already run once)")
+        grad_pred = ctx.model._backward(grad_out, ctx.shape, ctx.normalize, ctx.entry)
+        ctx.entry.release()
+        return grad_pred, None, None, None
 
 
 def load_vgg_lpips(lin_path, backbone_path, device="cuda"):

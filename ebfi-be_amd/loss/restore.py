@@ -1,6 +1,8 @@
 """Drop-in for the evaluation metrics of `loss.restore` (loss/restore.py:13-92): the reference's call contract -- a 1 x C x H x W
 pair in, a Python float out -- computed by ebfi_amd.metrics on the device instead of scikit-image on the host.  CharbonnierLoss (loss/restore.py:95-105, the
 validation score of the trainer) is the device implementation of ebfi_amd.loss."""
+import torch
+
 from ebfi_amd.loss import CharbonnierLoss  # noqa: F401
 from ebfi_amd.metrics import LPIPS_UNAVAILABLE, frame_metrics
 
@@ -24,7 +26,10 @@ class perceptual_loss:
     """LPIPS (v0.1) on the device, from the two weight files named here: lin_path, the reference's
     loss/PerceptualSimilarity/models/weights/v0.1/alex.pth, and backbone_path, torchvision's AlexNet state dict
     (alexnet-owt-7be5be79.pth); with net='vgg', v0.1/vgg.pth and torchvision's VGG-16 state dict (vgg16-397923af.pth).
-    Without them it raises: no weight cache is searched.  net='squeeze' is refused."""
+    Without them it raises: no weight cache is searched.  net='squeeze' is refused.
+    With net='vgg', grad mode on and a pred that requires grad, the call is the reference's training loss: the value goes through
+    VggLPIPS.loss and differentiates into pred (the per-channel average of other channel counts too).  net='alex' is a score
+    only, with or without grad mode: its trunk has no data-gradient kernels."""
 
     def __init__(self, weight=1.0, net='alex', use_gpu=True, gpu_ids=[0], lin_path=None, backbone_path=None):
         if lin_path is None or backbone_path is None:
@@ -38,10 +43,13 @@ class perceptual_loss:
         read as three (the reference's loop).  Returns weight * mean over N, a 0-dim device tensor."""
         assert pred.size() == target.size()
         c = pred.shape[1]
+        model = self.model
+        if getattr(model, "NET", None) == "vgg" and torch.is_grad_enabled() and pred.requires_grad:
+            model = model.loss                  # the training loss: the same value with a graph into pred
         if c in (1, 3):
-            dist = self.model(pred, target, normalize=normalize)
+            dist = model(pred, target, normalize=normalize)
         else:
-            dist = sum(self.model(pred[:, i:i + 1], target[:, i:i + 1], normalize=normalize) for i in range(c)) / c
+            dist = sum(model(pred[:, i:i + 1], target[:, i:i + 1], normalize=normalize) for i in range(c)) / c
         return self.weight * dist.mean()
 
 

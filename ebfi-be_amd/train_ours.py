@@ -19,6 +19,9 @@ valid_psnr, valid_ssim; recorded clips of valid_dataloader / --valid-data, or a 
 takes the best / early-stop decision of eval_model_performance, a best stamp writes checkpoint-iteration{it}.pth AND
 model_best_until_iteration{it}.pth, and trainer.monitor_best travels through --resume.  Unlike the reference, every rank
 holds the rank-averaged values and takes the same decision.  TensorBoard and image dumps of the reference are out of scope.
+The reference's perceptual_loss(net='vgg') (train_ours.py:765) is an optional term: `--lpips_weight W` (or trainer.lpips_weight)
+with `--lpips_lin` / `--lpips_backbone` adds W x LPIPS(Sharp, target), mean over the batch, to the loss above, differentiated by
+ebfi_amd.lpips on the device inside the (captured) step; the log line then names the term.  Off (W = 0) by default.
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train_ours.py -c config/train_ours.yml -id run
     python train_ours.py -c config/train_ours.yml -id run --iterations 20
@@ -104,6 +107,20 @@ def validation_settings(config, cli_valid_data=None):
             "batch_size": None if vd.get("batch_size") is None else int(vd["batch_size"]),
             "drop_last": bool(vd.get("drop_last", False)),
             "dataset": vd.get("dataset") or {}}
+
+
+def perceptual_settings(config, args):
+    """(weight, lin_path, backbone_path) of the LPIPS (VGG-16) term of the training loss: --lpips_weight, else trainer.lpips_weight,
+    else 0 = off.  A positive weight without both weight files ends the run: no weight cache is searched."""
+    tr = config.get("trainer", {}) or {}
+    weight = float(tr.get("lpips_weight", 0.0) if args.lpips_weight is None else args.lpips_weight)
+    if weight < 0:
+        raise SystemExit("train_ours.py: --lpips_weight / trainer.lpips_weight must not be negative, got %g" % weight)
+    if weight > 0 and (args.lpips_lin is None or args.lpips_backbone is None):
+        missing = " and ".join(f for f, v in (("--lpips_lin", args.lpips_lin), ("--lpips_backbone", args.lpips_backbone)) if v is None)
+        raise SystemExit("train_ours.py: an LPIPS weight of %g needs both weight files: --lpips_lin (the v0.1 vgg.pth heads) and "
+                         "--lpips_backbone (torchvision's VGG-16 state dict, vgg16-397923af.pth); missing %s" % (weight, missing))
+    return weight, args.lpips_lin, args.lpips_backbone
 
 
 class Monitor:
@@ -284,10 +301,11 @@ def run_validation(eng, batches, tracker, stamp, log_step=50, rank=0):
 
 
 def train_loop(eng, next_micro_batch, samples_per_pass, unit, st, vs, scheduler, monitor, valid_batches, tracker, out_dir, config,
-               rank, world, start):
+               rank, world, start, loss_note=""):
     """The iteration body of both trainers, from iteration `start` on: accu_step passes on `next_micro_batch(it, micro)`, log,
     validate, monitor, checkpoint, early stop, scheduler gate.  samples_per_pass / unit: what one pass of one rank adds to the
-    logged rate and the word it is logged under ('frames' -> frames/s).  Returns the iteration count it ended at."""
+    logged rate and the word it is logged under ('frames' -> frames/s); loss_note: what the log line says after the loss value
+    (the terms it holds beyond the reference's).  Returns the iteration count it ended at."""
     # throughput is counted from the end of the first iteration after which the engine is in its steady state (the first ones
     # pay module load, allocator growth, the just-in-time calibration of the fp16 operand scales and, with --graph, the
     # capture: GraphStepper.settled): what is logged is the steady-state rate, whole job (all ranks)
@@ -304,8 +322,8 @@ def train_loop(eng, next_micro_batch, samples_per_pass, unit, st, vs, scheduler,
         if rank == 0 and log_now:
             torch.cuda.synchronize()
             rate = samples / (time.perf_counter() - t0) if t0 is not None and samples else float("nan")
-            print("Iteration: %d/%d train_loss: %.4e learning rate: %.4e  %.1f %s/s"
-                  % (it, st["iterations"], loss.item(), lr_now, rate, unit), flush=True)
+            print("Iteration: %d/%d train_loss: %.4e%s learning rate: %.4e  %.1f %s/s"
+                  % (it, st["iterations"], loss.item(), loss_note, lr_now, rate, unit), flush=True)
         if t0 is None and eng.settled:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -339,7 +357,7 @@ def train_loop(eng, next_micro_batch, samples_per_pass, unit, st, vs, scheduler,
     return it
 
 
-def main():
+def get_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("-c", "--config", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "config", "train_ours.yml"))
     ap.add_argument("-id", "--runid", default="run")
@@ -369,10 +387,23 @@ def main():
     ap.add_argument("--raw-events", action="store_true",
                     help="build the event tensor from synthetic raw event lists with the device events_to_stack kernel "
                          "(the reference's data path, h5dataset.py:327-352) instead of drawing voxel counts directly")
+    ap.add_argument("--lpips_weight", type=float, default=None,
+                    help="add W x LPIPS (VGG-16, v0.1; the reference's perceptual_loss(net='vgg')) of the restored frame to the "
+                         "training loss, differentiated on the device (default: trainer.lpips_weight of the config, else 0 = off); "
+                         "needs --lpips_lin and --lpips_backbone")
+    ap.add_argument("--lpips_lin", type=str, default=None,
+                    help="LPIPS: the reference's linear heads, loss/PerceptualSimilarity/models/weights/v0.1/vgg.pth")
+    ap.add_argument("--lpips_backbone", type=str, default=None,
+                    help="LPIPS: torchvision's VGG-16 state dict (vgg16-397923af.pth of the torch hub cache)")
     add_loader_arguments(ap)
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = get_args(argv)
     with open(args.config) as fh:
         config = yaml.safe_load(fh)
+    lpips_weight, lpips_lin, lpips_backbone = perceptual_settings(config, args)      # (refuses before any device work)
     tr = config.get("trainer", {}) or {}
     st = trainer_settings(config, args.iterations)
     vs = validation_settings(config, args.valid_data)
@@ -382,10 +413,17 @@ def main():
     assert config["optimizer"]["name"] == "Adam", "only Adam (config/train_ours.yml) is implemented"
     oargs = config["optimizer"].get("args", {}) or {}
 
+    perceptual, loss_note = None, ""
+    if lpips_weight > 0:
+        from ebfi_amd.loss import PerceptualTerm
+        from ebfi_amd.lpips import load_vgg_lpips
+        perceptual = PerceptualTerm(load_vgg_lpips(lpips_lin, lpips_backbone, device=device), lpips_weight)
+        loss_note = " (with %g x lpips_vgg)" % lpips_weight
     eng = Engine(config["model"]["args"], device=device, precision=args.precision, lr=float(oargs.get("lr", 1e-4)),
                  betas=tuple(oargs.get("betas", (0.9, 0.999))), seed=args.seed,      # same init on every rank
                  graph=args.graph or bool(tr.get("graph", False)), accu_step=st["accu_step"],
-                 backward_f16=False if args.no_f16_backward else None, forward_f16=None if args.no_f16_forward else "filters")
+                 backward_f16=False if args.no_f16_backward else None, forward_f16=None if args.no_f16_forward else "filters",
+                 perceptual=perceptual)
     scheduler = build_lr_scheduler(config, eng.optimizer.inner)
     # monitor / best checkpoint / early stop (train_ours.py:155-163): only with validation on -- otherwise monitor_best stays None
     monitor = Monitor(vs["monitor"], vs["early_stop"],
@@ -414,7 +452,7 @@ def main():
                     on_device=not args.host_data)
 
     it = train_loop(eng, next_micro_batch, B, "frames", st, vs, scheduler, monitor, valid_batches, tracker, out_dir, config, rank,
-                    world, start)
+                    world, start, loss_note=loss_note)
     if real is not None:
         real.close()                     # (joins the loader's worker thread)
     if rank == 0 and eng.book is not None:

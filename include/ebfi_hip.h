@@ -96,7 +96,8 @@ extern "C" {
  *      ebfi_esim_loop_bound / _init / _count / _emit (the event simulator of the synthetic-dataset step), likewise; and
  *      ebfi_avgpool2_forward / ebfi_bilinear_up2_forward / ebfi_flow_max_magnitude / ebfi_slomo_assemble / _blend / _frame_u8
  *      (the frame-upsampling step), likewise -- with them ebfi_conv2d_forward accepts ksize 5 at stride 1, which it refused; and
- *      ebfi_lpips_vgg_params_bytes / _pack_params / _workspace / ebfi_lpips_vgg (evaluation LPIPS, VGG-16 v0.1), likewise */
+ *      ebfi_lpips_vgg_params_bytes / _pack_params / _workspace / ebfi_lpips_vgg (evaluation LPIPS, VGG-16 v0.1), likewise; and
+ *      ebfi_lpips_vgg_train_workspace / ebfi_lpips_vgg_forward_train / ebfi_lpips_vgg_backward (the same as a training loss) */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -723,6 +724,43 @@ int64_t ebfi_lpips_vgg_workspace(int64_t N, int C, int H, int W);
 int ebfi_lpips_vgg(const float *pred, const int64_t pred_strides[4], const float *target, const int64_t target_strides[4],
                    int64_t N, int C, int H, int W, int normalize, const void *params, void *workspace, int64_t workspace_bytes,
                    float *out_lpips, float *out_layers, void *stream);
+
+/* ------------------------------------------------------------------ LPIPS (VGG-16, v0.1) as a training loss
+ * The reference's perceptual_loss(net='vgg') is a loss (train_ours.py:765): autograd carries it into the prediction.  Here
+ * ebfi_lpips_vgg_forward_train takes the arguments of ebfi_lpips_vgg and writes the same out_lpips / out_layers, bit for bit
+ * (the same kernels on the same values in the same order of sums: each image's convolution tiles do not depend on the batch they
+ * are launched in), and keeps in `workspace` (at least ebfi_lpips_vgg_train_workspace(N, C, H, W) bytes, pure host arithmetic, 0
+ * for a shape ebfi_lpips_vgg refuses) what the backward needs: the 13 ReLU outputs of the pred images, the 5 tap maps of the
+ * target images and the non-finite flags, beside two maps [N][64][H][W] the target's other layers and then the gradients
+ * alternate between.  (2.00 GB per 720 x 1280 pair, 1.14 GB for 8 pairs of 256 x 256.)
+ *
+ * ebfi_lpips_vgg_backward reads that workspace (of the forward_train call with the same N, C, H, W, normalize and params; it
+ * writes the gradient maps into it, so one backward per forward) and grad_out, device float[N], the gradient with respect to
+ * lpips[n], and fully overwrites grad_pred [N, C, H, W] fp32 through grad_pred_strides (elements; column stride 1).  The target
+ * gets no gradient.  Per pair n, tap layer l of size H_l x W_l and pixel p, with x = f0(p) the pred features, y = f1(p) the
+ * target's:
+ *   n0 = sqrt(sum_c x_c^2), r0 = 1 / (n0 + 1e-10); n1, r1 likewise of y
+ *   a_c = 2 w_c (r0 x_c - r1 y_c)
+ *   S = sum_c a_c x_c = 2 (r0 sum_c w_c x_c^2 - r1 sum_c w_c x_c y_c)
+ *   dL/dx_k = grad_out[n] / (H_l W_l) * (a_k r0 - x_k r0^2 S / n0);  exactly 0 for every k where n0 == 0
+ * (at n0 == 0 every x_k is a ReLU zero, which the mask of the convolution's data gradient removes in torch as well; the kernel
+ * writes the zero itself, because that mask is a product and 0 * NaN is NaN).  The sums are formed in fp64 from the fp32 maps.
+ * One fused kernel per tap layer mirrors the forward's: it adds to dL/dx the gradient of the pooled map that the next block
+ * returned (none for f5), routed to the first maximum of each 2x2 window in row-major order (torch's rule; the last row / column
+ * of an odd map gets a tap gradient and no routed one), and writes the sum for the pred images.  The 13 data gradients are
+ * ebfi_conv2d_backward_data (EBFI_F32, act = 1 at slope 0: the ReLU mask read from the saved output) between the two gradient
+ * maps, pred images only.  Input epilogue, with mul_c = (normalize ? 2 : 1) / scale_c: grad_pred[n, c] = mul_c * grad_x'[n, c]
+ * for C == 3, the sum over the three c for C == 1.  A pair whose pred or target held a NaN or Inf (the forward's flags) gets
+ * grad_pred[n] NaN everywhere; no other pair is touched by it.
+ * Both follow the launch contract of ebfi_lpips_alex (on `stream` only, no host synchronisation, no allocation, no atomics:
+ * capturable and bit-reproducible) and its error codes; argument errors touch no GPU.  The AlexNet trunk stays forward-only: its
+ * 11x11 stride-4 and 5x5 layers have no data-gradient kernel here. */
+int64_t ebfi_lpips_vgg_train_workspace(int64_t N, int C, int H, int W);
+int ebfi_lpips_vgg_forward_train(const float *pred, const int64_t pred_strides[4], const float *target,
+                                 const int64_t target_strides[4], int64_t N, int C, int H, int W, int normalize, const void *params,
+                                 void *workspace, int64_t workspace_bytes, float *out_lpips, float *out_layers, void *stream);
+int ebfi_lpips_vgg_backward(const float *grad_out, const void *params, void *workspace, int64_t workspace_bytes, int64_t N, int C,
+                            int H, int W, int normalize, float *grad_pred, const int64_t grad_pred_strides[4], void *stream);
 
 /* ------------------------------------------------------------------ Charbonnier loss (validation)
  * CharbonnierLoss of the reference (loss/restore.py:95-105; the validation score of train_ours.py:588) per sample n of an fp32

@@ -10,7 +10,13 @@ depend on the weights).  Prints one JSON line per shape: microseconds per call, 
                         (FLOPs / peak: arithmetic from the shapes, not a measurement), per-kernel rows from the library's event
                         profiler (a separate pass: its events serialise the launches), and the AlexNet figure of the same call
 
-usage: python tools/lpipsbench.py [iters] [--net {alex,vgg}]"""
+  --net vgg --backward  the training loss: VggLPIPS.loss forward + backward (ebfi_lpips_vgg_forward_train / _backward) at
+                        8 x 3 x 256 x 256 and at one 720 x 1280 pair: mean and spread per step, the forward alone, per-kernel rows
+                        from the event profiler (the tap adjoint's bytes and rate among them), the 64 -> 3 data gradient timed
+                        alone and its share, the training workspace, and -- as context: it is what the reference runs -- PyTorch
+                        eager autograd through the same trunk (F.conv2d / F.max_pool2d / F.relu in float32) on the same device
+
+usage: python tools/lpipsbench.py [iters] [--net {alex,vgg}] [--backward]"""
 import argparse
 import json
 import os
@@ -116,6 +122,100 @@ def bench_vgg(vgg, alex, N_, C, H, W, iters):
     return row
 
 
+def time_steps(step, iters):
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for t0, t1 in ev:
+        t0.record()
+        step()
+        t1.record()
+    torch.cuda.synchronize()
+    us = [t0.elapsed_time(t1) * 1e3 for t0, t1 in ev]
+    return dict(us_mean=round(sum(us) / len(us), 1), us_min=round(min(us), 1), us_max=round(max(us), 1))
+
+
+def torch_eager_loss(ws, bs, hs, pred, target):
+    """The reference's path: the same trunk and distances as torch ops in float32 (normalize=True), lpips [N]."""
+    import torch.nn.functional as F
+    shift = torch.tensor([-0.030, -0.088, -0.188], device=pred.device).view(1, 3, 1, 1)
+    scale = torch.tensor([0.458, 0.448, 0.450], device=pred.device).view(1, 3, 1, 1)
+    blocks = (2, 2, 3, 3, 3)
+
+    def taps(x):
+        x, out, i = (2 * x - 1 - shift) / scale, [], 0
+        for k, n in enumerate(blocks):
+            if k:
+                x = F.max_pool2d(x, 2, 2)
+            for _ in range(n):
+                x = F.relu(F.conv2d(x, ws[i], bs[i], padding=1))
+                i += 1
+            out.append(x)
+        return out
+
+    unit = lambda f: f / (torch.sqrt((f ** 2).sum(1, keepdim=True)) + 1e-10)     # noqa: E731
+    with torch.no_grad():
+        t_taps = taps(target)
+    total = 0
+    for f0, f1, h in zip(taps(pred), t_taps, hs):
+        total = total + (h.view(1, -1, 1, 1) * (unit(f0) - unit(f1)) ** 2).sum(1).mean((1, 2))
+    return total
+
+
+def bench_vgg_backward(vgg, weights, N_, C, H, W, iters):
+    pred, target = pair(N_, C, H, W)
+    pred.requires_grad_(True)
+
+    def step():
+        pred.grad = None
+        vgg.loss(pred, target).sum().backward()
+
+    def forward_only():
+        with torch.no_grad():
+            vgg.loss(pred, target)
+
+    row = dict(net="vgg", mode="forward_train+backward", shape=[N_, C, H, W],
+               train_workspace_bytes=int(N.lib().ebfi_lpips_vgg_train_workspace(N_, C, H, W)),
+               score_workspace_bytes=int(N.lib().ebfi_lpips_vgg_workspace(N_, C, H, W)))
+    row["step"] = time_steps(step, iters)
+    row["forward_train"] = time_steps(forward_only, iters)
+    row["score"] = time_steps(lambda: vgg(pred.detach(), target), iters)
+
+    class Both:                                    # (kernel_rows calls model(pred, target))
+        def __call__(self, p, t):
+            step()
+
+    row["kernels"] = kernel_rows(Both(), pred, target, min(iters, 3))
+    # the first layer's data gradient (64 -> 3 on the generic tile) alone
+    go, y = torch.randn(N_, 64, H, W, device="cuda"), torch.rand(N_, 64, H, W, device="cuda")
+    gi, w0 = torch.empty(N_, 3, H, W, device="cuda"), vgg._keep[0][0]
+
+    def dgrad0():
+        rc = N.lib().ebfi_conv2d_backward_data(N.ptr(go), N.ptr(y), N.ptr(w0), N.ptr(gi), N_, 3, H, W, 64, 3, 1, 1, 1, 0.0, N.EBFI_F32,
+                                               N.stream_ptr(vgg.device))
+        N.check(rc, "ebfi_conv2d_backward_data")
+
+    row["dgrad_64_to_3"] = time_steps(dgrad0, iters)
+    backward_us = row["step"]["us_mean"] - row["forward_train"]["us_mean"]
+    row["backward_us"] = round(backward_us, 1)
+    row["dgrad_64_to_3_share_of_backward"] = round(row["dgrad_64_to_3"]["us_mean"] / max(backward_us, 1e-9), 3)
+    dg = row["kernels"].get("conv_fwd_f32/dgrad")
+    if dg:
+        row["dgrad_share_of_backward_kernels"] = round(
+            dg["us_per_call"] / max(sum(v["us_per_call"] for k, v in row["kernels"].items()
+                                        if k in ("conv_fwd_f32/dgrad", "lpips_vgg_tap_bwd", "lpips_vgg_epilogue")), 1e-9), 3)
+    ws, bs, hs = ([t.to("cuda") for t in part] for part in weights)
+
+    def eager_step():
+        pred.grad = None
+        torch_eager_loss(ws, bs, hs, pred, target).sum().backward()
+
+    row["torch_eager_step"] = time_steps(eager_step, iters)
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def random_weights(shapes, heads, g):
     ws = [torch.randn(s, generator=g) * (2.0 / (s[1] * s[2] * s[3])) ** 0.5 for s in shapes]
     bs = [0.01 + 0.05 * torch.rand(s[0], generator=g) for s in shapes]
@@ -127,7 +227,10 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("iters", type=int, nargs="?", default=10)
     ap.add_argument("--net", choices=("alex", "vgg"), default="alex")
+    ap.add_argument("--backward", action="store_true", help="with --net vgg: time the training loss (forward_train + backward)")
     a = ap.parse_args()
+    if a.backward and a.net != "vgg":
+        ap.error("--backward needs --net vgg: the AlexNet trunk is forward-only")
     assert torch.cuda.is_available(), "lpipsbench needs the MI355X"
     g = torch.Generator().manual_seed(0)
     alex = AlexLPIPS(*random_weights(CONV_SHAPES, [s[0] for s in CONV_SHAPES], g), "cuda")
@@ -135,6 +238,11 @@ if __name__ == "__main__":
         bench(alex, 16, 3, 720, 1280, a.iters)
         bench(alex, 16, 3, 256, 256, a.iters)
     else:
-        vgg = VggLPIPS(*random_weights(VGG_CONV_SHAPES, VGG_HEAD_CHANNELS, g), "cuda")
+        weights = random_weights(VGG_CONV_SHAPES, VGG_HEAD_CHANNELS, g)
+        vgg = VggLPIPS(*weights, "cuda")
+        if a.backward:
+            bench_vgg_backward(vgg, weights, 8, 3, 256, 256, a.iters)
+            bench_vgg_backward(vgg, weights, 1, 3, 720, 1280, a.iters)
+            sys.exit(0)
         bench_vgg(vgg, alex, 1, 3, 720, 1280, a.iters)
         bench_vgg(vgg, alex, 16, 3, 256, 256, a.iters)
