@@ -162,6 +162,8 @@ SIGNATURES = {
     "ebfi_period_frames_u8": (_i, [_vp, _p64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ebfi_event_cnt_image_workspace": (_i64, [_i64, _i, _i, _i]),
     "ebfi_event_cnt_image": (_i, [_vp, _p64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "ebfi_segment_stats_workspace": (_i64, [_i64, _i]),
+    "ebfi_segment_stats": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "ebfi_esim_loop_bound": (_i64, [_vp, _c.c_double, _c.c_double]),
     "ebfi_esim_init": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "ebfi_esim_count": (_i, [_vp, _p64, _i, _i64, _i, _i, _vp, _vp, _c.c_double, _c.c_double, _c.c_double, _vp, _vp, _vp]),

@@ -119,6 +119,10 @@ class Engine(graphstep.GraphStepper):
         # third step on magnitudes move by a few percent per step and the delayed scales (f16scale) take over.
         self.calibration_steps = 2
         self.perceptual = perceptual if train else None
+        # ebfi_amd.monitor (images on): sample 0 of the restored frame of every pass is kept in `panel_sharp` -- one small copy inside
+        # the (captured) step -- and `validate` leaves (Frame, Event, last Final, last LatentF) in `last_valid_panels`.  Off by
+        # default: not one launch of the step changes.  Set before the first step (a graph holds what it was captured with).
+        self.keep_panels, self.panel_sharp, self.last_valid_panels = False, None, None
         if train:
             self.model.train()
             self.loss = TrainLoss(self.model_args.get("DetailEnabled", True)).to(self.device)
@@ -166,6 +170,10 @@ class Engine(graphstep.GraphStepper):
             if book is not None and self._steps_run < self.calibration_steps:
                 book.calibrated.clear()             # (measure every operand of this pass again, see __init__)
             sharp_pre, sharp = self.model(frame, event, t, gtex)
+            if self.keep_panels:
+                if self.panel_sharp is None or self.panel_sharp.shape[1:] != sharp.shape[1:]:
+                    self.panel_sharp = torch.empty((1,) + tuple(sharp.shape[1:]), dtype=torch.float32, device=sharp.device)
+                self.panel_sharp.copy_(sharp.detach()[:1])
             loss = self.loss(sharp_pre.float(), sharp.float(), target, self.iteration, self.accu_step)
             if self.perceptual is not None:
                 loss = loss + self.perceptual(sharp.float(), target) / self.accu_step
@@ -260,6 +268,8 @@ class Engine(graphstep.GraphStepper):
         loss = charbonnier_per_sample(pred, target, eps).double().sum() / num_i
         psnr, ssim, _ = frame_metrics(pred, target)
         values = torch.stack([loss, psnr.double().mean(), ssim.double().mean()])
+        if self.keep_panels:
+            self.last_valid_panels = (frame, event, final[:, -1], latent[:, -1])
         return {k: values[i] for i, k in enumerate(self.VALID_KEYS)}
 
 

@@ -18,7 +18,9 @@ every valid_step-th iteration Engine.validate scores the validation set (valid_l
 valid_psnr, valid_ssim; recorded clips of valid_dataloader / --valid-data, or a fixed set of synthetic batches), `Monitor`
 takes the best / early-stop decision of eval_model_performance, a best stamp writes checkpoint-iteration{it}.pth AND
 model_best_until_iteration{it}.pth, and trainer.monitor_best travels through --resume.  Unlike the reference, every rank
-holds the rank-averaged values and takes the same decision.  TensorBoard and image dumps of the reference are out of scope.
+holds the rank-averaged values and takes the same decision.  The reference's TensorBoard log (:283-319, :594-616) is written by
+ebfi_amd.monitor into <output_path>/log/<experiment>/<runid>/ when trainer.tensorboard or --tensorboard asks for it (scalars;
+images with trainer.vis.enabled; per-layer weight / gradient statistics with trainer.telemetry.stats_step); off by default.
 The reference's perceptual_loss(net='vgg') (train_ours.py:765) is an optional term: `--lpips_weight W` (or trainer.lpips_weight)
 with `--lpips_lin` / `--lpips_backbone` adds W x LPIPS(Sharp, target), mean over the batch, to the loss above, differentiated by
 ebfi_amd.lpips on the device inside the (captured) step; the log line then names the term.  Off (W = 0) by default.
@@ -234,6 +236,27 @@ def add_loader_arguments(ap):
                          "ahead while the current batch trains; 0 = everything synchronously in the training loop")
 
 
+def add_monitor_arguments(ap):
+    """--tensorboard / --no-tensorboard of both trainers: override trainer.tensorboard of the config."""
+    ap.add_argument("--tensorboard", dest="tensorboard", action="store_true", default=None,
+                    help="write a TensorBoard event file (ebfi_amd.monitor) into <output_path>/log/<experiment>/<runid>/ whatever "
+                         "trainer.tensorboard says: scalars, images with trainer.vis.enabled, per-layer statistics with "
+                         "trainer.telemetry.stats_step")
+    ap.add_argument("--no-tensorboard", dest="tensorboard", action="store_false",
+                    help="write no event file whatever trainer.tensorboard says")
+
+
+def build_monitor(config, args, runid, rank, eng, default_experiment="Ours"):
+    """The run's ebfi_amd.monitor.TrainMonitor, attached to the engine, or None when neither the config nor the flag asks for one
+    (nothing of ebfi_amd.monitor is imported then)."""
+    tr = config.get("trainer", {}) or {}
+    on = bool(tr.get("tensorboard", False)) if getattr(args, "tensorboard", None) is None else bool(args.tensorboard)
+    if not on:
+        return None
+    from ebfi_amd import monitor as M
+    return M.TrainMonitor(M.monitor_settings(config, on), M.log_directory(config, runid, default_experiment), rank=rank).attach(eng)
+
+
 DEFAULT_EXPOSURE_TIME = [9, 10, 11, 12, 13, 14, 15]      # ExposureTime of the reference's train_ours.yml (Custom exposure)
 
 
@@ -283,10 +306,11 @@ def validation_batches(vs, config, args, B, H, W, TB, device, rank, world):
     return lambda: iter(mine)
 
 
-def run_validation(eng, batches, tracker, stamp, log_step=50, rank=0):
+def run_validation(eng, batches, tracker, stamp, log_step=50, rank=0, telemetry=None):
     """_valid of the reference (train_ours.py:545-619) for one stamp: every (batch, load) is scored by Engine.validate, averaged
     over ranks (reduce_tensor: ONE collective and ONE host read per (batch, load), none per timestamp) and averaged over the
-    stamp by the MetricTracker.  Every rank feeds its tracker with the same reduced values.  Returns tracker.result()."""
+    stamp by the MetricTracker.  Every rank feeds its tracker with the same reduced values.  Returns tracker.result().
+    telemetry: an ebfi_amd.monitor.TrainMonitor that logs every (batch, load), or None."""
     tracker.reset()
     for k, batch in enumerate(batches()):
         loads = batch["SeqLatentF"].shape[1] if isinstance(batch, dict) else 1
@@ -295,30 +319,38 @@ def run_validation(eng, batches, tracker, stamp, log_step=50, rank=0):
             host = reduce_tensor(torch.stack([vals[key] for key in eng.VALID_KEYS])).tolist()
             for key, v in zip(eng.VALID_KEYS, host):
                 tracker.update(key, v)
+            if telemetry is not None:
+                telemetry.valid_batch(host[0], eng)
             if rank == 0 and k % log_step == 0:
                 print("Valid timestamp: %d [batch %d] valid_loss: %.4e" % (stamp, k, host[0]), flush=True)
     return tracker.result()
 
 
 def train_loop(eng, next_micro_batch, samples_per_pass, unit, st, vs, scheduler, monitor, valid_batches, tracker, out_dir, config,
-               rank, world, start, loss_note=""):
+               rank, world, start, loss_note="", telemetry=None):
     """The iteration body of both trainers, from iteration `start` on: accu_step passes on `next_micro_batch(it, micro)`, log,
     validate, monitor, checkpoint, early stop, scheduler gate.  samples_per_pass / unit: what one pass of one rank adds to the
     logged rate and the word it is logged under ('frames' -> frames/s); loss_note: what the log line says after the loss value
-    (the terms it holds beyond the reference's).  Returns the iteration count it ended at."""
+    (the terms it holds beyond the reference's).  telemetry: an ebfi_amd.monitor.TrainMonitor (one per rank) or None; None leaves
+    every line below as it runs without one.  Returns the iteration count it ended at."""
     # throughput is counted from the end of the first iteration after which the engine is in its steady state (the first ones
     # pay module load, allocator growth, the just-in-time calibration of the fp16 operand scales and, with --graph, the
     # capture: GraphStepper.settled): what is logged is the steady-state rate, whole job (all ranks)
     t0, samples, it, valid_stamp = None, 0, start, 1
     while it < st["iterations"]:
         for micro in range(st["accu_step"]):
-            loss = eng.train_step(*next_micro_batch(it, micro))
+            batch = next_micro_batch(it, micro)
+            loss = eng.train_step(*batch)
             if t0 is not None:
                 samples += samples_per_pass * world
         log_now = it % st["log_step"] == 0 or it == st["iterations"] - 1
-        if log_now:                      # the loss all-reduce is for logging only (train_ours.py:278-279): do it when logging
-            loss = reduce_tensor(loss.clone())
         lr_now = scheduler.get_last_lr()[0] if scheduler is not None else eng.optimizer.param_groups[0]["lr"]
+        if telemetry is not None:
+            telemetry.after_step(it, loss, lr_now, eng, batch)
+            if log_now:                  # (the monitor's ring holds this iteration's loss: its flush is the log line's all-reduce)
+                loss = torch.tensor(telemetry.flush())
+        elif log_now:                    # the loss all-reduce is for logging only (train_ours.py:278-279): do it when logging
+            loss = reduce_tensor(loss.clone())
         if rank == 0 and log_now:
             torch.cuda.synchronize()
             rate = samples / (time.perf_counter() - t0) if t0 is not None and samples else float("nan")
@@ -331,7 +363,10 @@ def train_loop(eng, next_micro_batch, samples_per_pass, unit, st, vs, scheduler,
         best = stop = False
         if vs["do_validation"] and it % vs["valid_step"] == 0 and it != 0:
             t_valid = time.perf_counter()
-            val_log = run_validation(eng, valid_batches, tracker, valid_stamp, vs["valid_log_step"], rank)
+            val_log = run_validation(eng, valid_batches, tracker, valid_stamp, vs["valid_log_step"], rank, telemetry=telemetry)
+            if telemetry is not None:
+                telemetry.stamp(valid_stamp, val_log)
+                telemetry.pause(time.perf_counter() - t_valid)
             if t0 is not None:           # (the logged rate is the training rate: the stamp's time is taken off the clock)
                 t0 += time.perf_counter() - t_valid
             stop, best = monitor.evaluate(val_log)
@@ -396,6 +431,7 @@ def get_args(argv=None):
     ap.add_argument("--lpips_backbone", type=str, default=None,
                     help="LPIPS: torchvision's VGG-16 state dict (vgg16-397923af.pth of the torch hub cache)")
     add_loader_arguments(ap)
+    add_monitor_arguments(ap)
     return ap.parse_args(argv)
 
 
@@ -451,8 +487,11 @@ def main(argv=None):
         return make(B, H, W, TB, device=device, seed=args.seed + 1000 * (it * st["accu_step"] + micro), rank=rank,
                     on_device=not args.host_data)
 
+    telemetry = build_monitor(config, args, args.runid, rank, eng)
     it = train_loop(eng, next_micro_batch, B, "frames", st, vs, scheduler, monitor, valid_batches, tracker, out_dir, config, rank,
-                    world, start, loss_note=loss_note)
+                    world, start, loss_note=loss_note, telemetry=telemetry)
+    if telemetry is not None:
+        telemetry.close()
     if real is not None:
         real.close()                     # (joins the loader's worker thread)
     if rank == 0 and eng.book is not None:

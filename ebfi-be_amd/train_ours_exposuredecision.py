@@ -28,8 +28,8 @@ import yaml
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
-from train_ours import (CHECKPOINT_KEYS, TRAINING_MODE, Monitor, add_loader_arguments, best_checkpoint_name,  # noqa: E402,F401
-                        build_lr_scheduler, checkpoint_state, clip_dataset, init_distributed_mode, resume_checkpoint, save_checkpoint,
+from train_ours import (CHECKPOINT_KEYS, TRAINING_MODE, Monitor, add_loader_arguments, add_monitor_arguments,  # noqa: E402,F401
+                        best_checkpoint_name, build_lr_scheduler, build_monitor, checkpoint_state, clip_dataset, init_distributed_mode, resume_checkpoint, save_checkpoint,
                         train_loop, trainer_settings, validation_seeds, validation_settings)
 from ebfi_amd.exposure_engine import (BLURRY_FASHIONS, check_fashion, check_model_name,  # noqa: E402,F401
                                       synthetic_exposure_batch)
@@ -64,6 +64,7 @@ def build_parser():
                     help="validation clips instead of valid_dataloader.path_to_datalist_txt (with trainer.do_validation; without "
                          "either: a fixed set of trainer.valid_batches synthetic batches)")
     add_loader_arguments(ap)
+    add_monitor_arguments(ap)
     return ap
 
 
@@ -161,8 +162,11 @@ def main(argv=None):
                                         seed=args.seed + 1000 * (it * st["accu_step"] + micro), rank=rank,
                                         on_device=not args.host_data)
 
+    telemetry = build_monitor(config, args, runid, rank, eng, default_experiment="ExposurePretrain")
     train_loop(eng, next_micro_batch, B, "samples", st, vs, scheduler, monitor, valid_batches, tracker, out_dir, config, rank, world,
-               start)
+               start, telemetry=telemetry)
+    if telemetry is not None:
+        telemetry.close()
     if real is not None:
         real.close()                     # (joins the loader's worker thread)
     if world > 1:

@@ -41,6 +41,8 @@
  *   ebfi_period_frames_u8       GetFrames of the synthetic-blur reader (dataloader/h5dataset.py:296-311): sharp frames + exposure mean
  *   ebfi_event_cnt_image        event_visualisation.plot_event_cnt of the evaluation loop (infer_ours.py:139-142,
  *                               myutils/vis_events/matplotlib_plot_events.py:127-251)
+ *   ebfi_segment_stats          per-layer weight / gradient moments and histograms of the training monitor (no counterpart in the
+ *                               reference: its TensorBoard log holds scalars and images only)
  *   ebfi_esim_*                 esim_py.EventSimulator of the dataset step (generate_dataset/syn_gopro.py:77-81,115-116)
  *   ebfi_avgpool2_forward / ebfi_bilinear_up2_forward / ebfi_flow_max_magnitude / ebfi_slomo_*
  *                               the Vid2E adaptive upsampler (generate_dataset/upsampling/utils/{upsampler,model}.py)
@@ -97,7 +99,9 @@ extern "C" {
  *      ebfi_avgpool2_forward / ebfi_bilinear_up2_forward / ebfi_flow_max_magnitude / ebfi_slomo_assemble / _blend / _frame_u8
  *      (the frame-upsampling step), likewise -- with them ebfi_conv2d_forward accepts ksize 5 at stride 1, which it refused; and
  *      ebfi_lpips_vgg_params_bytes / _pack_params / _workspace / ebfi_lpips_vgg (evaluation LPIPS, VGG-16 v0.1), likewise; and
- *      ebfi_lpips_vgg_train_workspace / ebfi_lpips_vgg_forward_train / ebfi_lpips_vgg_backward (the same as a training loss) */
+ *      ebfi_lpips_vgg_train_workspace / ebfi_lpips_vgg_forward_train / ebfi_lpips_vgg_backward (the same as a training loss); and
+ *      ebfi_segment_stats_workspace / ebfi_segment_stats (per-layer weight and gradient statistics of the training monitor),
+ *      likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -883,6 +887,27 @@ int64_t ebfi_event_cnt_image_workspace(int64_t n, int H, int W, int is_norm);
 int ebfi_event_cnt_image(const float *ev, const int64_t ev_strides[3], int64_t n, int H, int W, int color_scheme,
                          int is_black_background, int is_norm, int use_opencv, uint8_t *out, void *workspace,
                          int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ per-segment statistics of a flat buffer (training monitor)
+ * ebfi_segment_stats: x float32 [n]; offsets int64 [S + 1] ON THE DEVICE (segment s = x[offsets[s] .. offsets[s + 1]); the entry
+ * point never reads them, the kernels clamp them into [0, n] and make them ascending, so no table can take a load out of
+ * bounds); limits float64 [nb] on the device, ascending.  For every segment:
+ *   moments[s] = {finite count, non-finite count, min, max, sum, sum of squares}   float64 [S][6], over the FINITE values
+ *   hist[s][i] = number of finite values v with limits[i - 1] < v <= limits[i]      int32 [S][nb]; bucket 0 starts at -inf, a
+ *                value above the last limit counts in the last bucket
+ * NaN and +-Inf count in the non-finite column only.  An empty segment gives counts 0, min +inf, max -inf, sums 0.  Every
+ * value is widened to float64 first: comparisons, sums and squares are float64; the limits table is staged in LDS and searched
+ * by bisection (no log / pow); counts are integer adds (LDS, then global).  Sums are folded in one fixed order (per thread in
+ * index order, a fixed tree over the workgroup, a fixed fold over the segment's chunks of 4096 elements): two calls on the same
+ * data give the same bits.  The work split depends on n, S and the offsets only.
+ * workspace: ebfi_segment_stats_workspace(n, S) bytes (host arithmetic), 16-byte aligned, overwritten by every call.  Three
+ * launches (the clearing of hist, the chunks, the per-segment fold) go onto `stream`, with no allocation and no host
+ * synchronisation: capturable.
+ * Null pointers, n < 0, S < 0, nb outside 1..2048, a misaligned workspace -> EBFI_ERR_ARG; a missing or short workspace ->
+ * EBFI_ERR_WORKSPACE; a grid beyond 2^31 - 1 -> EBFI_ERR_UNSUPPORTED; none of them touches the GPU.  S == 0 is a no-op. */
+int64_t ebfi_segment_stats_workspace(int64_t n, int S);
+int ebfi_segment_stats(const float *x, int64_t n, const int64_t *offsets, int S, const double *limits, int nb, double *moments,
+                       int32_t *hist, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------ event simulator of the synthetic-dataset step
  * What generate_dataset/syn_gopro.py:77-81,115-116 asks of esim_py.EventSimulator: events from a run of gray uint8 frames.  esim_py
