@@ -57,6 +57,146 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float *__restrict__ p, c
         for (int64_t k = n4 * 4; k < n; ++k) upd(p[k], g[k], m[k], v[k]);
 }
 
+// The optimiser section of the config beyond plain Adam (ebfi_amd.dp.FlatOptimizer; the reference builds its optimiser with
+// eval(config['optimizer']['name'])(params, **config['optimizer']['args']), train_ours.py:770-771): Adam / AdamW with weight
+// decay and AMSGrad, and SGD with weight decay, momentum, dampening and Nesterov, each as ONE launch over the flat buffer with
+// the guard protocol of adam_flat_kernel.  Every option is a template parameter, so a variant loads and stores only the maps
+// it needs: plain SGD 3 (p read + written, g read), SGD with momentum 5, Adam 7, AMSGrad 9.  `g` is only read: weight decay is
+// added in registers, never into the gradient buffer (the all-reduce's wire buffer, which telemetry reads after the step).
+// The arithmetic is torch's single-tensor step operation by operation, with the roundings of its float32 CPU kernels spelled
+// out (contraction off, an explicit fma exactly where add(alpha=) / lerp / addcmul fuse):
+//   Adam   g' = fma(p, wd, g) (L2)  |  p <- p (1 - lr wd) (decoupled);  m <- fma(1-b1, g' - m, m);
+//          v <- fma((1-b2) g', g', b2 v);  vmax <- max(vmax, v);  p <- p - (lr/c1 m) / (sqrt(v | vmax) / sqrt(c2) + eps)
+//   SGD    d = fma(p, wd, g);  buf <- d on the first applied step, fma(d, 1-dampening, momentum buf) afterwards;
+//          d <- fma(buf, momentum, d) (Nesterov) | buf;  p <- fma(d, -lr, p)
+// "First applied step" is step[0] == 1 on the device: the host increments the word before the launch and a skipped step
+// takes it back, so a first step skipped by the overflow guard leaves the next one the first.
+enum { WD_NONE = 0, WD_L2 = 1, WD_DECOUPLED = 2 };
+enum { MOM_NONE = 0, MOM_PLAIN = 1, MOM_NESTEROV = 2 };
+
+struct OptimArgs {
+    double lr, beta1, beta2, eps, weight_decay, momentum, dampening;
+};
+
+struct AdamCoef {
+    float step_size, c2s, w1, b2, w2, eps, wd, keep;
+};
+
+template <int WD, bool AMS>
+__device__ __forceinline__ void adam_elem(float &pp, float gg, float &mm, float &vv, float &xx, const AdamCoef &c) {
+#pragma clang fp contract(off)
+    if (WD == WD_L2) gg = __builtin_fmaf(pp, c.wd, gg);
+    if (WD == WD_DECOUPLED) pp = pp * c.keep;
+    mm = __builtin_fmaf(c.w1, gg - mm, mm);
+    vv = __builtin_fmaf(c.w2 * gg, gg, vv * c.b2);
+    float s = vv;
+    if (AMS) {
+        xx = (xx != xx || xx >= vv) ? xx : vv;          // torch.maximum: a NaN on either side stays
+        s = xx;
+    }
+    const float denom = sqrtf(s) / c.c2s + c.eps;
+    pp = pp - (c.step_size * mm) / denom;
+}
+
+struct SgdCoef {
+    float neg_lr, wd, mom, undamp;
+    bool first;
+};
+
+template <int WD, int MOM>
+__device__ __forceinline__ void sgd_elem(float &pp, float gg, float &bb, const SgdCoef &c) {
+#pragma clang fp contract(off)
+    float d = gg;
+    if (WD == WD_L2) d = __builtin_fmaf(pp, c.wd, gg);
+    if (MOM != MOM_NONE) {
+        bb = c.first ? d : __builtin_fmaf(d, c.undamp, bb * c.mom);
+        d = MOM == MOM_NESTEROV ? __builtin_fmaf(bb, c.mom, d) : bb;
+    }
+    pp = __builtin_fmaf(d, c.neg_lr, pp);
+}
+
+// guard / flag: the protocol of adam_flat_kernel, word for word (plain SGD has no step word: nothing to take back there)
+__device__ __forceinline__ bool optim_skipped(float *__restrict__ step, int *__restrict__ guard, const float *__restrict__ flag) {
+    if (guard != nullptr) {
+        const bool by_flag = flag != nullptr && !(flag[0] == 0.f);
+        if (guard[0] != 0 || by_flag) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) {
+                if (step != nullptr) step[0] -= 1.f;
+                guard[1] += 1;
+                if (by_flag) guard[0] = 1;
+            }
+            return true;
+        }
+    }
+    return false;
+}
+
+template <int WD, bool AMS>
+__global__ __launch_bounds__(256) void adam_opt_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                       float *__restrict__ v, float *__restrict__ vmax, float *__restrict__ step,
+                                                       int64_t n4, int64_t n, OptimArgs a, int *__restrict__ guard,
+                                                       const float *__restrict__ flag) {
+    if (optim_skipped(step, guard, flag)) return;
+    const double t = (double)step[0];
+    const double c1 = 1.0 - pow(a.beta1, t), c2 = 1.0 - pow(a.beta2, t);
+    AdamCoef c;
+    c.step_size = (float)(a.lr / c1), c.c2s = (float)sqrt(c2);
+    c.w1 = (float)(1.0 - a.beta1), c.b2 = (float)a.beta2, c.w2 = (float)(1.0 - a.beta2), c.eps = (float)a.eps;
+    c.wd = (float)a.weight_decay, c.keep = (float)(1.0 - a.lr * a.weight_decay);
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n4) {
+        float4 P = reinterpret_cast<float4 *>(p)[i], M = reinterpret_cast<float4 *>(m)[i], V = reinterpret_cast<float4 *>(v)[i];
+        const float4 G = reinterpret_cast<const float4 *>(g)[i];
+        float4 X = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (AMS) X = reinterpret_cast<float4 *>(vmax)[i];
+        adam_elem<WD, AMS>(P.x, G.x, M.x, V.x, X.x, c);
+        adam_elem<WD, AMS>(P.y, G.y, M.y, V.y, X.y, c);
+        adam_elem<WD, AMS>(P.z, G.z, M.z, V.z, X.z, c);
+        adam_elem<WD, AMS>(P.w, G.w, M.w, V.w, X.w, c);
+        reinterpret_cast<float4 *>(p)[i] = P;
+        reinterpret_cast<float4 *>(m)[i] = M;
+        reinterpret_cast<float4 *>(v)[i] = V;
+        if (AMS) reinterpret_cast<float4 *>(vmax)[i] = X;
+    }
+    if (i == 0)
+        for (int64_t k = n4 * 4; k < n; ++k) {
+            float x = 0.f;
+            if (AMS) x = vmax[k];
+            adam_elem<WD, AMS>(p[k], g[k], m[k], v[k], x, c);
+            if (AMS) vmax[k] = x;
+        }
+}
+
+template <int WD, int MOM>
+__global__ __launch_bounds__(256) void sgd_opt_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ buf,
+                                                      float *__restrict__ step, int64_t n4, int64_t n, OptimArgs a,
+                                                      int *__restrict__ guard, const float *__restrict__ flag) {
+    if (optim_skipped(step, guard, flag)) return;
+    SgdCoef c;
+    c.neg_lr = (float)(-a.lr), c.wd = (float)a.weight_decay, c.mom = (float)a.momentum, c.undamp = (float)(1.0 - a.dampening);
+    c.first = MOM != MOM_NONE && step[0] == 1.f;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n4) {
+        float4 P = reinterpret_cast<float4 *>(p)[i];
+        const float4 G = reinterpret_cast<const float4 *>(g)[i];
+        float4 B = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (MOM != MOM_NONE) B = reinterpret_cast<float4 *>(buf)[i];
+        sgd_elem<WD, MOM>(P.x, G.x, B.x, c);
+        sgd_elem<WD, MOM>(P.y, G.y, B.y, c);
+        sgd_elem<WD, MOM>(P.z, G.z, B.z, c);
+        sgd_elem<WD, MOM>(P.w, G.w, B.w, c);
+        reinterpret_cast<float4 *>(p)[i] = P;
+        if (MOM != MOM_NONE) reinterpret_cast<float4 *>(buf)[i] = B;
+    }
+    if (i == 0)
+        for (int64_t k = n4 * 4; k < n; ++k) {
+            float b = 0.f;
+            if (MOM != MOM_NONE) b = buf[k];
+            sgd_elem<WD, MOM>(p[k], g[k], b, c);
+            if (MOM != MOM_NONE) buf[k] = b;
+        }
+}
+
 // Gradient packing of the training step (ebfi_amd.dp.FlatGradBucket.gather): the per-parameter gradient tensors autograd
 // produced are copied into the one flat buffer the all-reduce and the Adam launch work on.  The source pointers travel BY VALUE
 // in the kernel arguments, 128 tensors per launch (3 launches for the model's 255 parameters) -- nothing to upload, and a
@@ -200,4 +340,84 @@ extern "C" int ebfi_adam_step_guarded(float *param, const float *grad, float *ex
                            exp_avg, exp_avg_sq, step, n4, n, lr, beta1, beta2, eps, guard, flag);
     }
     return check_launch("adam_flat");
+}
+
+namespace {
+
+template <int WD, bool AMS>
+void launch_adam_opt(const char *label, double maps, float *p, const float *g, float *m, float *v, float *vmax, float *step,
+                     int64_t n, const OptimArgs &a, int *guard, const float *flag, hipStream_t st) {
+    const int64_t n4 = n / 4;
+    ProfScope ps(label, st, 0.0, maps * 4.0 * (double)n);
+    hipLaunchKernelGGL((adam_opt_kernel<WD, AMS>), dim3((unsigned)ceil_div(std::max<int64_t>(n4, 1), 256)), dim3(256), 0, st, p, g,
+                       m, v, vmax, step, n4, n, a, guard, flag);
+}
+
+template <int WD, int MOM>
+void launch_sgd_opt(const char *label, double maps, float *p, const float *g, float *buf, float *step, int64_t n, const OptimArgs &a,
+                    int *guard, const float *flag, hipStream_t st) {
+    const int64_t n4 = n / 4;
+    ProfScope ps(label, st, 0.0, maps * 4.0 * (double)n);
+    hipLaunchKernelGGL((sgd_opt_kernel<WD, MOM>), dim3((unsigned)ceil_div(std::max<int64_t>(n4, 1), 256)), dim3(256), 0, st, p, g,
+                       buf, step, n4, n, a, guard, flag);
+}
+
+}  // namespace
+
+extern "C" int ebfi_optim_step(int kind, int flags, float *param, const float *grad, float *state0, float *state1, float *state2,
+                               float *step, int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                               double momentum, double dampening, int *guard, const float *flag, void *stream) {
+    if (kind != EBFI_OPTIM_ADAM && kind != EBFI_OPTIM_SGD)
+        return fail(EBFI_ERR_UNSUPPORTED, "optim_step: unknown optimiser kind %d", kind);
+    const int known = kind == EBFI_OPTIM_ADAM ? (EBFI_OPTIM_DECOUPLED_DECAY | EBFI_OPTIM_AMSGRAD) : EBFI_OPTIM_NESTEROV;
+    if (flags & ~known) return fail(EBFI_ERR_ARG, "optim_step: option flags 0x%x do not belong to optimiser kind %d", flags, kind);
+    if (!(weight_decay >= 0.0)) return fail(EBFI_ERR_ARG, "optim_step: weight_decay must not be negative");
+    const bool ams = (flags & EBFI_OPTIM_AMSGRAD) != 0, decoupled = (flags & EBFI_OPTIM_DECOUPLED_DECAY) != 0;
+    if (kind == EBFI_OPTIM_ADAM && !ams && weight_decay == 0.0)         // the default configuration: the launch it has always been
+        return ebfi_adam_step_guarded(param, grad, state0, state1, step, n, lr, beta1, beta2, eps, guard, flag, stream);
+    if (flag && !guard) return fail(EBFI_ERR_ARG, "optim_step: an overflow flag needs the guard words");
+    if (!param || !grad || n < 0) return fail(EBFI_ERR_ARG, "optim_step: null argument");
+    if (!aligned16(param) || !aligned16(grad)) return fail(EBFI_ERR_ARG, "optim_step: buffers must be 16-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const OptimArgs a{lr, beta1, beta2, eps, weight_decay, momentum, dampening};
+    if (kind == EBFI_OPTIM_ADAM) {
+        if (!state0 || !state1 || !step || (ams && !state2))
+            return fail(EBFI_ERR_ARG, "optim_step: Adam needs exp_avg, exp_avg_sq%s and the step word", ams ? ", max_exp_avg_sq" : "");
+        if (!aligned16(state0) || !aligned16(state1) || (ams && !aligned16(state2)))
+            return fail(EBFI_ERR_ARG, "optim_step: buffers must be 16-byte aligned");
+        if (n == 0) return EBFI_OK;
+        const int wd = weight_decay == 0.0 ? WD_NONE : decoupled ? WD_DECOUPLED : WD_L2;
+        const double maps = ams ? 9.0 : 7.0;
+#define EBFI_ADAM_CASE(W, A, L) \
+    if (wd == W && ams == A) launch_adam_opt<W, A>(L, maps, param, grad, state0, state1, state2, step, n, a, guard, flag, st)
+        EBFI_ADAM_CASE(WD_L2, false, "optim_adam_l2");
+        EBFI_ADAM_CASE(WD_DECOUPLED, false, "optim_adamw");
+        EBFI_ADAM_CASE(WD_NONE, true, "optim_adam_ams");
+        EBFI_ADAM_CASE(WD_L2, true, "optim_adam_l2_ams");
+        EBFI_ADAM_CASE(WD_DECOUPLED, true, "optim_adamw_ams");
+#undef EBFI_ADAM_CASE
+        return check_launch("optim_adam");
+    }
+    const bool nesterov = (flags & EBFI_OPTIM_NESTEROV) != 0;
+    if (!(momentum >= 0.0)) return fail(EBFI_ERR_ARG, "optim_step: momentum must not be negative");
+    if (nesterov && (momentum <= 0.0 || dampening != 0.0))
+        return fail(EBFI_ERR_ARG, "optim_step: Nesterov momentum requires a momentum and zero dampening");
+    const int mom = momentum == 0.0 ? MOM_NONE : nesterov ? MOM_NESTEROV : MOM_PLAIN;
+    if (mom != MOM_NONE && (!state0 || !step))
+        return fail(EBFI_ERR_ARG, "optim_step: SGD with momentum needs the momentum buffer and the step word");
+    if (mom != MOM_NONE && !aligned16(state0)) return fail(EBFI_ERR_ARG, "optim_step: buffers must be 16-byte aligned");
+    if (n == 0) return EBFI_OK;
+    const int wd = weight_decay == 0.0 ? WD_NONE : WD_L2;
+    const double maps = mom == MOM_NONE ? 3.0 : 5.0;
+    float *word = mom == MOM_NONE ? nullptr : step;      // (plain SGD keeps no count: its kernel never reads one)
+#define EBFI_SGD_CASE(W, M, L) \
+    if (wd == W && mom == M) launch_sgd_opt<W, M>(L, maps, param, grad, state0, word, n, a, guard, flag, st)
+    EBFI_SGD_CASE(WD_NONE, MOM_NONE, "optim_sgd");
+    EBFI_SGD_CASE(WD_L2, MOM_NONE, "optim_sgd_l2");
+    EBFI_SGD_CASE(WD_NONE, MOM_PLAIN, "optim_sgd_mom");
+    EBFI_SGD_CASE(WD_L2, MOM_PLAIN, "optim_sgd_l2_mom");
+    EBFI_SGD_CASE(WD_NONE, MOM_NESTEROV, "optim_sgd_nesterov");
+    EBFI_SGD_CASE(WD_L2, MOM_NESTEROV, "optim_sgd_l2_nesterov");
+#undef EBFI_SGD_CASE
+    return check_launch("optim_sgd");
 }

@@ -193,17 +193,56 @@ class FlatGradBucket:
         return all(p.grad is not None and p.grad.untyped_storage().data_ptr() == base for p in self.params)
 
 
-class FlatAdam:
-    """Adam over ONE flat parameter buffer.
+SUPPORTED_OPTIMIZERS = ("Adam", "AdamW", "SGD")
+# optimizer.args entries that say HOW a process runs the update, not what it computes: this process decides them
+_RUN_MODE_ARGS = ("foreach", "fused", "capturable")
+_OPTIM_ADAM, _OPTIM_SGD = 0, 1                                # include/ebfi_hip.h EBFI_OPTIM_*
+_OPTIM_DECOUPLED_DECAY, _OPTIM_AMSGRAD, _OPTIM_NESTEROV = 1, 2, 4
+
+
+def _refuse_group(name, group):
+    """Options the one-launch update does not implement are refused, never ignored."""
+    for key in ("maximize", "differentiable"):
+        if group.get(key):
+            raise ValueError("optimizer %s: %s=True is not supported by the flat one-launch update" % (name, key))
+    if torch.is_tensor(group.get("lr")):
+        raise ValueError("optimizer %s: a tensor lr is not supported (hyper-parameters travel by value; set "
+                         "param_groups[0]['lr'] to a float, as the LR schedulers do)" % name)
+
+
+def optimizer_arguments(name, args=None):
+    """Validate an `optimizer` section (config['optimizer']['name'] / ['args'], the reference's eval(name)(params, **args),
+    train_ours.py:770-771) without touching a device -> the arguments FlatOptimizer passes to torch.optim.<name>.
+    Supported: Adam, AdamW, SGD, with every argument of the torch class except maximize / differentiable / a tensor lr
+    (ValueError); foreach / fused / capturable are run-mode flags this process decides and are dropped.  Torch's own
+    constructor checks apply (negative lr, nesterov without momentum, an unknown keyword)."""
+    if name not in SUPPORTED_OPTIMIZERS:
+        raise ValueError("optimizer '%s' is not supported: the flat one-launch update implements %s"
+                         % (name, ", ".join(SUPPORTED_OPTIMIZERS)))
+    args = {k: v for k, v in dict(args or {}).items() if k not in _RUN_MODE_ARGS}
+    _refuse_group(name, args)
+    if "betas" in args:
+        args["betas"] = tuple(float(b) for b in args["betas"])
+    try:
+        getattr(torch.optim, name)([torch.nn.Parameter(torch.zeros(1))], **args)
+    except TypeError as e:
+        raise ValueError("optimizer %s: %s" % (name, e)) from e
+    return args
+
+
+class FlatOptimizer:
+    """torch.optim.Adam, AdamW or SGD over ONE flat parameter buffer.
 
     The trainable parameters are re-pointed at views of a single contiguous buffer (their values, names and shapes do
-    not change), the packed gradient of `FlatGradBucket` becomes that buffer's `.grad`, and the update is one fused
-    launch over 5.7 M elements instead of a multi-tensor pass over 255 tensors.  Same arithmetic as
-    ``torch.optim.Adam(params, lr, betas, eps)`` (it IS torch's fused Adam, applied to one tensor).
-    `state_dict()` / `load_state_dict()` speak torch's per-parameter layout -- what the reference's checkpoints hold
-    (train_ours.py:621-671) -- so checkpoints stay interchangeable."""
+    not change), the packed gradient of `FlatGradBucket` becomes that buffer's `.grad`, and the update is one native
+    launch over 5.7 M elements (csrc/optim.hip) instead of a multi-tensor pass over 255 tensors.  `inner` is
+    ``getattr(torch.optim, name)([flat], **args)``: it owns hyper-parameters and state, torch's defaults and constructor
+    checks apply, and LR schedulers work on it.  `state_dict()` / `load_state_dict()` speak torch's per-parameter layout
+    of that class -- what the reference's checkpoints hold (train_ours.py:621-671) -- so checkpoints stay interchangeable."""
 
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, params, name="Adam", **args):
+        args = optimizer_arguments(name, args)
+        self.name = name
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError("no trainable parameters")
@@ -215,7 +254,10 @@ class FlatAdam:
             p.data = flat[off:off + p.numel()].view_as(p)
             off += p.numel()
         self.flat = torch.nn.Parameter(flat)
-        self.inner = torch.optim.Adam([self.flat], lr=lr, betas=betas, eps=eps, amsgrad=False, fused=bool(flat.is_cuda))
+        self.inner = getattr(torch.optim, name)([self.flat], fused=bool(flat.is_cuda), **args)
+        # SGD with momentum on the device: 0 until the first APPLIED step (the overflow guard takes a skipped one back), so
+        # the kernel knows when `buf <- d` holds.  Private: torch's SGD state has no step and the exported state shows none.
+        self._sgd_step = None
 
     @property
     def param_groups(self):
@@ -232,7 +274,8 @@ class FlatAdam:
             raise ValueError("an overflow flag needs the guard tensor that counts the skipped steps")
         if self._native_step(flat_grad, guard, flag):
             return
-        if guard is not None:                                     # torch's own step (CPU / unusual options): host-side check
+        _refuse_group(self.name, self.inner.param_groups[0])
+        if guard is not None:                                     # torch's own step (CPU tensors): host-side check
             if flag is not None and not float(flag[0]) == 0.0:
                 guard[0] = 1
             if int(guard[0].item()) != 0:
@@ -243,34 +286,56 @@ class FlatAdam:
         self.flat.grad = None
 
     def _native_step(self, flat_grad, guard=None, flag=None):
-        """The update as ONE bandwidth-bound launch of libebfi_hip.so (csrc/optim.hip) on the state tensors of the inner
-        torch.optim.Adam (which keeps owning hyper-parameters, state and checkpoint layout).  CPU tensors, weight decay,
-        amsgrad or maximize take torch's own step."""
+        """The update as ONE bandwidth-bound launch of libebfi_hip.so (csrc/optim.hip, ebfi_optim_step) on the state tensors
+        of the inner torch optimiser (which keeps owning hyper-parameters, state and checkpoint layout): every supported
+        configuration on a CUDA float32 buffer, whatever param_groups says at this step.  Only CPU tensors take torch's own
+        step."""
         from . import _native as N
         grp = self.inner.param_groups[0]
         if not (self.flat.is_cuda and self.flat.dtype == torch.float32 and flat_grad.dtype == torch.float32 and
-                flat_grad.is_contiguous() and not grp.get("amsgrad") and not grp.get("maximize") and
-                float(grp.get("weight_decay", 0.0)) == 0.0 and not torch.is_tensor(grp["lr"])):
+                flat_grad.is_contiguous()):
             return False
+        _refuse_group(self.name, grp)
+        dev = self.flat.device
         st = self.inner.state[self.flat]
-        if not st:
-            st["step"] = torch.zeros((), dtype=torch.float32, device=self.flat.device)
-            st["exp_avg"] = torch.zeros_like(self.flat.data)
-            st["exp_avg_sq"] = torch.zeros_like(self.flat.data)
-        if not (torch.is_tensor(st["step"]) and st["step"].is_cuda):
-            st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32, device=self.flat.device)
+        zeros = lambda: torch.zeros_like(self.flat.data)
+        b1 = b2 = eps = momentum = dampening = 0.0
+        if self.name == "SGD":
+            kind, flags = _OPTIM_SGD, _OPTIM_NESTEROV if grp["nesterov"] else 0
+            momentum, dampening = float(grp["momentum"]), float(grp["dampening"])
+            states, word = [None, None, None], None
+            if momentum != 0.0:
+                if self._sgd_step is None:                        # (a loaded momentum_buffer: the first step has been taken)
+                    taken = st.get("momentum_buffer") is not None
+                    self._sgd_step = torch.full((), 1.0 if taken else 0.0, dtype=torch.float32, device=dev)
+                if st.get("momentum_buffer") is None:
+                    st["momentum_buffer"] = zeros()
+                states[0], word = st["momentum_buffer"], self._sgd_step
+        else:
+            kind = _OPTIM_ADAM
+            flags = (_OPTIM_DECOUPLED_DECAY if grp.get("decoupled_weight_decay") else 0) | (_OPTIM_AMSGRAD if grp["amsgrad"] else 0)
+            (b1, b2), eps = grp["betas"], grp["eps"]
+            if "step" not in st:
+                st["step"] = torch.zeros((), dtype=torch.float32, device=dev)
+            if not (torch.is_tensor(st["step"]) and st["step"].is_cuda):
+                st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32, device=dev)
+            for key in ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if grp["amsgrad"] else ()):
+                if key not in st:
+                    st[key] = zeros()
+            states, word = [st["exp_avg"], st["exp_avg_sq"], st.get("max_exp_avg_sq") if grp["amsgrad"] else None], st["step"]
         # the bookkeeping torch's own step() wrapper does: step hooks, and the marks the LR schedulers look at
         # (`_opt_called`: without it every scheduler.step() warns "lr_scheduler.step() before optimizer.step()")
         opt = self.inner
         for hook in list(getattr(opt, "_optimizer_step_pre_hooks", {}).values()):
             hook(opt, (), {})
-        st["step"] += 1
-        b1, b2 = grp["betas"]
+        if word is not None:
+            word += 1
         with torch.cuda.device_of(self.flat):
-            rc = N.lib().ebfi_adam_step_guarded(N.ptr(self.flat.data), N.ptr(flat_grad), N.ptr(st["exp_avg"]), N.ptr(st["exp_avg_sq"]),
-                                                N.ptr(st["step"]), self.flat.numel(), float(grp["lr"]), float(b1), float(b2),
-                                                float(grp["eps"]), N.ptr(guard), N.ptr(flag), N.stream_ptr(self.flat.device))
-        N.check(rc, "ebfi_adam_step_guarded")
+            rc = N.lib().ebfi_optim_step(kind, flags, N.ptr(self.flat.data), N.ptr(flat_grad), N.ptr(states[0]), N.ptr(states[1]),
+                                         N.ptr(states[2]), N.ptr(word), self.flat.numel(), float(grp["lr"]), float(b1), float(b2),
+                                         float(eps), float(grp["weight_decay"]), momentum, dampening, N.ptr(guard), N.ptr(flag),
+                                         N.stream_ptr(dev))
+        N.check(rc, "ebfi_optim_step")
         opt._opt_called = True
         if hasattr(opt, "_step_count"):
             opt._step_count += 1
@@ -282,15 +347,28 @@ class FlatAdam:
         base = self.flat.untyped_storage().data_ptr()
         return all(p.untyped_storage().data_ptr() == base for p in self.params)
 
+    def _slices(self):
+        return [(i, p, slice(off, off + p.numel())) for i, (p, off) in enumerate(zip(self.params, self._offsets))]
+
     def state_dict(self):
+        """torch's state_dict() of the class in question, per parameter.  Adam family: step, exp_avg, exp_avg_sq, and
+        max_exp_avg_sq with amsgrad.  SGD: momentum_buffer once a step with momentum has been APPLIED (reads the device's
+        step word: a checkpoint may synchronise), nothing before, nothing without momentum."""
         st = self.inner.state.get(self.flat, {})
+        grp = self.inner.param_groups[0]
         state = {}
-        if st:
-            for i, (p, off) in enumerate(zip(self.params, self._offsets)):
-                sl = slice(off, off + p.numel())
-                state[i] = {"step": st["step"].clone() if torch.is_tensor(st["step"]) else st["step"],
-                            "exp_avg": st["exp_avg"][sl].view_as(p).clone(), "exp_avg_sq": st["exp_avg_sq"][sl].view_as(p).clone()}
-        group = {k: v for k, v in self.inner.param_groups[0].items() if k != "params"}
+        if self.name == "SGD":
+            buf = st.get("momentum_buffer")
+            started = buf is not None and (self._sgd_step is None or float(self._sgd_step) > 0.0)
+            if started and grp["momentum"] != 0:
+                for i, p, sl in self._slices():
+                    state[i] = {"momentum_buffer": buf[sl].view_as(p).clone()}
+        elif st:
+            keys = ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if grp["amsgrad"] and "max_exp_avg_sq" in st else ())
+            for i, p, sl in self._slices():
+                state[i] = {"step": st["step"].clone() if torch.is_tensor(st["step"]) else st["step"]}
+                state[i].update((k, st[k][sl].view_as(p).clone()) for k in keys)
+        group = {k: v for k, v in grp.items() if k != "params"}
         group["lr"] = float(group["lr"])
         group["params"] = list(range(len(self.params)))
         return {"state": state, "param_groups": [group]}
@@ -301,35 +379,76 @@ class FlatAdam:
     _LOCAL_KEYS = ("params", "fused", "foreach", "capturable", "differentiable")
 
     def load_state_dict(self, sd):
-        """Accepts torch's per-parameter Adam layout (what the reference's checkpoints hold, train_ours.py:621-671).
-        Parameters without an entry (never received a gradient before the save) start from zero moments.  All parameters
+        """Accepts torch's per-parameter layout of the class (what the reference's checkpoints hold, train_ours.py:621-671);
+        hyper-parameters of its param_groups override the constructor's, as in torch.
+        Parameters without an entry (never received a gradient before the save), and a buffer the checkpoint does not
+        carry (max_exp_avg_sq of an Adam checkpoint loaded into an AMSGrad run), start from zero.  All parameters
         share ONE step counter here (the update is one launch over the flat buffer, missing gradients count as zero), so
         the per-parameter steps of the checkpoint must agree -- they do whenever every parameter had a gradient on every
         step, which is the case for this model; a checkpoint whose steps differ (parameters frozen for part of the run) is
-        refused instead of being silently re-timed."""
+        refused instead of being silently re-timed.  SGD: a checkpoint that holds a momentum_buffer has taken its first step."""
         groups = sd["param_groups"]
         if len(groups) != 1 or len(groups[0]["params"]) != len(self.params):
             raise ValueError("optimizer state has %d parameters in %d group(s), this model trains %d"
                              % (sum(len(g["params"]) for g in groups), len(groups), len(self.params)))
+        grp = self.inner.param_groups[0]
         for k, v in groups[0].items():
-            if k not in self._LOCAL_KEYS and k in self.inner.param_groups[0]:
-                self.inner.param_groups[0][k] = v
+            if k not in self._LOCAL_KEYS and k in grp:
+                grp[k] = v
+        _refuse_group(self.name, grp)
+        self._sgd_step = None
         if not sd["state"]:
             self.inner.state.pop(self.flat, None)
             return
         ids = groups[0]["params"]
-        m, v = torch.zeros_like(self.flat.data), torch.zeros_like(self.flat.data)
-        step = None
-        for pid, p, off in zip(ids, self.params, self._offsets):
+        if self.name == "SGD":
+            keys = ("momentum_buffer",)
+        else:
+            keys = ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if grp["amsgrad"] else ())
+        bufs = {k: torch.zeros_like(self.flat.data) for k in keys}
+        step, found = None, False
+        for pid, (_, p, sl) in zip(ids, self._slices()):
             e = sd["state"].get(pid)
             if e is None:
                 continue
-            m[off:off + p.numel()] = e["exp_avg"].reshape(-1).to(m)
-            v[off:off + p.numel()] = e["exp_avg_sq"].reshape(-1).to(v)
+            for k in keys:
+                if e.get(k) is not None:
+                    bufs[k][sl] = e[k].reshape(-1).to(bufs[k])
+                    found = True
+            if self.name == "SGD":
+                continue
             if step is not None and float(e["step"]) != step:
-                raise ValueError("optimizer state holds different step counts per parameter (%g and %g): the flat Adam keeps "
-                                 "one counter for all parameters" % (step, float(e["step"])))
+                raise ValueError("optimizer state holds different step counts per parameter (%g and %g): the flat %s keeps "
+                                 "one counter for all parameters" % (step, float(e["step"]), self.name))
             step = float(e["step"])
+        if self.name == "SGD":
+            if found:
+                self.inner.state[self.flat] = bufs
+            else:
+                self.inner.state.pop(self.flat, None)
+            return
         step = 0.0 if step is None else step
         step = torch.tensor(step, dtype=torch.float32, device=self.flat.device if self.flat.is_cuda else "cpu")
-        self.inner.state[self.flat] = {"step": step, "exp_avg": m, "exp_avg_sq": v}
+        self.inner.state[self.flat] = dict(bufs, step=step)
+
+
+def build_flat_optimizer(params, optimizer=None, lr=1e-4, betas=(0.9, 0.999)):
+    """The engines' optimiser: None -> FlatAdam(lr, betas), exactly what they have always built; otherwise the config's
+    optimizer section {"name": ..., "args": {...}}, with the `lr=` / `betas=` keywords filling in what args leaves out
+    (betas only where the class has them)."""
+    if optimizer is None:
+        return FlatAdam(params, lr=lr, betas=tuple(betas))
+    name = optimizer.get("name", "Adam")
+    args = dict(optimizer.get("args") or {})
+    args.setdefault("lr", lr)
+    if name in ("Adam", "AdamW"):
+        args.setdefault("betas", tuple(betas))
+    return FlatOptimizer(params, name, **args)
+
+
+class FlatAdam(FlatOptimizer):
+    """torch.optim.Adam(params, lr, betas, eps) over one flat parameter buffer: FlatOptimizer with the defaults of the
+    shipped configs (no weight decay, no AMSGrad)."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
+        super().__init__(params, "Adam", lr=lr, betas=betas, eps=eps, amsgrad=False)

@@ -9,7 +9,7 @@ import contextlib
 import torch
 
 from . import graphstep
-from .dp import FlatAdam, FlatGradBucket, broadcast_parameters
+from .dp import FlatGradBucket, broadcast_parameters, build_flat_optimizer
 from .loss import TrainLoss
 from .model import EVFIAutoEx
 
@@ -85,9 +85,11 @@ def synthetic_validation_batch(B, H, W, TB=16, num_frames=4, device="cuda", seed
 class Engine(graphstep.GraphStepper):
     def __init__(self, model_args=None, device="cuda", precision="fp32", lr=1e-4, seed=None, train=True, graph=False,
                  accu_step=1, betas=(0.9, 0.999), backward_f16=None, forward_f16="filters", strict_graph=None,
-                 perceptual=None):
+                 perceptual=None, optimizer=None):
         """graph / accu_step / strict_graph: see graphstep.GraphStepper (a graph is captured per input shape, precision and loss
         phase).
+        optimizer: None = Adam with `lr` / `betas` (the shipped config), or the config's optimizer section {"name": "Adam" |
+        "AdamW" | "SGD", "args": {...}} (ebfi_amd.dp.FlatOptimizer); `lr` / `betas` fill in what its args leave out.
         perceptual: None, or an ebfi_amd.loss.PerceptualTerm: its value for (Sharp, target), / accu_step, is added to the training
         loss before the backward pass, inside the captured step.  The LPIPS weights are not model parameters: they are neither
         trained nor saved.  With None not one launch of the step changes.
@@ -130,7 +132,7 @@ class Engine(graphstep.GraphStepper):
             # one flat parameter buffer (parameters become views of it) updated by ONE fused Adam launch on the packed
             # gradient (0.4 ms per step less than the multi-tensor pass over 255 tensors); state_dict() keeps torch's
             # per-parameter layout for checkpoints
-            self.optimizer = FlatAdam(self.bucket.params, lr=lr, betas=tuple(betas))
+            self.optimizer = build_flat_optimizer(self.bucket.params, optimizer, lr, betas)
         else:
             self.model.eval()
         # MFMA operand images of every conv weight, refreshed by one launch per step instead of one per conv call

@@ -11,7 +11,7 @@ optimiser path of the main engine (ebfi_amd.graphstep.GraphStepper over ebfi_amd
 import torch
 
 from .blur import Frame2DCP, Frame2Lap
-from .dp import FlatAdam, FlatGradBucket, broadcast_parameters
+from .dp import FlatGradBucket, broadcast_parameters, build_flat_optimizer
 from .graphstep import GraphStepper
 from .loss import DutyMSELoss, duty_head
 from .model import ExposureDecision
@@ -77,10 +77,11 @@ class ExposureEngine(GraphStepper):
     VALID_KEYS = ("valid_loss", "valid_mae")
 
     def __init__(self, model_args=None, fashion="RGBLap", device="cuda", precision="fp32", lr=1e-4, seed=None, graph=False,
-                 accu_step=1, betas=(0.9, 0.999), strict_graph=None, name="ExposureDecision"):
+                 accu_step=1, betas=(0.9, 0.999), strict_graph=None, name="ExposureDecision", optimizer=None):
         """precision: 'fp32' (exact) or 'bf16x3' (split-precision matrix-core operands, fp32-grade accuracy) for the 3x3
         convolutions; the fp16-operand backward of the main engine is not used here.  graph / accu_step / strict_graph: see
-        graphstep.GraphStepper."""
+        graphstep.GraphStepper.  optimizer: None = Adam with `lr` / `betas`, or the config's optimizer section {"name", "args"}
+        (see Engine)."""
         check_model_name(name)
         if precision not in ("fp32", "bf16x3"):
             raise ValueError("precision must be 'fp32' or 'bf16x3'")
@@ -100,7 +101,7 @@ class ExposureEngine(GraphStepper):
         self.last_Ex = None
         self.loss = DutyMSELoss(1.0 / self.accu_step)
         self.bucket = FlatGradBucket(self.model)
-        self.optimizer = FlatAdam(self.bucket.params, lr=lr, betas=tuple(betas))
+        self.optimizer = build_flat_optimizer(self.bucket.params, optimizer, lr, betas)
         self.bank = None
         if self.device.type == "cuda" and precision == "bf16x3":
             from . import weightbank

@@ -125,6 +125,22 @@ def perceptual_settings(config, args):
     return weight, args.lpips_lin, args.lpips_backbone
 
 
+def optimizer_settings(config, args=None):
+    """{"name", "args"} of the optimiser from the config's `optimizer` section, the reference's
+    eval(config['optimizer']['name'])(trainable_params, **config['optimizer']['args']) (train_ours.py:770-771): Adam, AdamW or
+    SGD with all of optimizer.args (weight_decay, eps, amsgrad, momentum, ...; torch's defaults where the section is silent,
+    except lr: 1e-4 as it has always been here).  -lr / --learning_rate (stage 1) overrides args.lr.  Anything the native update does not implement -- another optimiser,
+    maximize, an argument the torch class does not know -- raises ValueError here, before any device work."""
+    from ebfi_amd.dp import optimizer_arguments
+    sec = config.get("optimizer") or {}
+    name = sec.get("name", "Adam")
+    oargs = dict(sec.get("args") or {})
+    if getattr(args, "learning_rate", None):
+        oargs["lr"] = float(args.learning_rate)
+    oargs["lr"] = float(oargs.get("lr", 1e-4))
+    return {"name": name, "args": optimizer_arguments(name, oargs)}
+
+
 class Monitor:
     """eval_model_performance of the reference (train_ours.py:155-163, :392-435), host-only.  monitor: 'off' or '<min|max> <key>'.
     `evaluate(log)` -> (stop_training, best): improved means <= / >= the best so far (a tie counts), a missing key warns and
@@ -440,14 +456,13 @@ def main(argv=None):
     with open(args.config) as fh:
         config = yaml.safe_load(fh)
     lpips_weight, lpips_lin, lpips_backbone = perceptual_settings(config, args)      # (refuses before any device work)
+    optimizer = optimizer_settings(config, args)                                      # (likewise)
     tr = config.get("trainer", {}) or {}
     st = trainer_settings(config, args.iterations)
     vs = validation_settings(config, args.valid_data)
     rank, world, gpu = init_distributed_mode()
     device = torch.device("cuda", gpu)
     assert config["model"]["name"] == "EVFIAutoEx", "only the EVFIAutoEx hot path is implemented"
-    assert config["optimizer"]["name"] == "Adam", "only Adam (config/train_ours.yml) is implemented"
-    oargs = config["optimizer"].get("args", {}) or {}
 
     perceptual, loss_note = None, ""
     if lpips_weight > 0:
@@ -455,8 +470,8 @@ def main(argv=None):
         from ebfi_amd.lpips import load_vgg_lpips
         perceptual = PerceptualTerm(load_vgg_lpips(lpips_lin, lpips_backbone, device=device), lpips_weight)
         loss_note = " (with %g x lpips_vgg)" % lpips_weight
-    eng = Engine(config["model"]["args"], device=device, precision=args.precision, lr=float(oargs.get("lr", 1e-4)),
-                 betas=tuple(oargs.get("betas", (0.9, 0.999))), seed=args.seed,      # same init on every rank
+    eng = Engine(config["model"]["args"], device=device, precision=args.precision, optimizer=optimizer,
+                 seed=args.seed,                                                      # same init on every rank
                  graph=args.graph or bool(tr.get("graph", False)), accu_step=st["accu_step"],
                  backward_f16=False if args.no_f16_backward else None, forward_f16=None if args.no_f16_forward else "filters",
                  perceptual=perceptual)

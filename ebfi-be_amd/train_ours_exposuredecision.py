@@ -29,8 +29,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 from train_ours import (CHECKPOINT_KEYS, TRAINING_MODE, Monitor, add_loader_arguments, add_monitor_arguments,  # noqa: E402,F401
-                        best_checkpoint_name, build_lr_scheduler, build_monitor, checkpoint_state, clip_dataset, init_distributed_mode, resume_checkpoint, save_checkpoint,
-                        train_loop, trainer_settings, validation_seeds, validation_settings)
+                        best_checkpoint_name, build_lr_scheduler, build_monitor, checkpoint_state, clip_dataset, init_distributed_mode,
+                        optimizer_settings, resume_checkpoint, save_checkpoint, train_loop, trainer_settings, validation_seeds, validation_settings)
 from ebfi_amd.exposure_engine import (BLURRY_FASHIONS, check_fashion, check_model_name,  # noqa: E402,F401
                                       synthetic_exposure_batch)
 
@@ -130,15 +130,14 @@ def main(argv=None):
     es = exposure_settings(config)
     if args.batch_size:
         es["batch_size"] = int(args.batch_size)
-    assert config["optimizer"]["name"] == "Adam", "only Adam (config/train_ours_exposuredecision.yml) is implemented"
+    optimizer = optimizer_settings(config, args)      # (-lr overrides optimizer.args.lr; refuses before any device work)
     rank, world, gpu = init_distributed_mode()
     device = torch.device("cuda", gpu)
-    oargs = config["optimizer"].get("args", {}) or {}
     from ebfi_amd.exposure_engine import ExposureEngine
     from ebfi_amd.metrics import MetricTracker
 
     eng = ExposureEngine(es["model_args"], fashion=es["fashion"], device=device, precision=args.precision,
-                         lr=float(args.learning_rate or oargs.get("lr", 1e-4)), betas=tuple(oargs.get("betas", (0.9, 0.999))), seed=args.seed,
+                         optimizer=optimizer, seed=args.seed,
                          graph=args.graph or bool(tr.get("graph", False)), accu_step=st["accu_step"], name=es["name"])
     scheduler = build_lr_scheduler(config, eng.optimizer.inner)
     monitor = Monitor(vs["monitor"], vs["early_stop"],

@@ -32,6 +32,7 @@
  *   ebfi_gauss5_*               GaussianConv of the Laplacian-pyramid loss (loss/restore.py:149-163)
  *   ebfi_laploss_*              whole Laplacian-pyramid L1 term of a step as one difference pyramid (loss/restore.py:166-213)
  *   ebfi_adam_step              optimizer.step() of train_ours.py:276-277 over the flat parameter buffer
+ *   ebfi_optim_step             the same for every optimiser the config may name: torch.optim.Adam / AdamW / SGD (train_ours.py:770-771)
  *   ebfi_grad_gather            gradient bucket packing of DistributedDataParallel (train_ours.py:754) as one launch
  *   ebfi_gather_sum             weight re-layouts of the depth-2 Conv3d / ConvTranspose3d (models/model_misc/resnet_3D.py)
  *   ebfi_events_to_stack        dataloader/encodings.py:307-350 (events_to_stack)
@@ -101,7 +102,8 @@ extern "C" {
  *      ebfi_lpips_vgg_params_bytes / _pack_params / _workspace / ebfi_lpips_vgg (evaluation LPIPS, VGG-16 v0.1), likewise; and
  *      ebfi_lpips_vgg_train_workspace / ebfi_lpips_vgg_forward_train / ebfi_lpips_vgg_backward (the same as a training loss); and
  *      ebfi_segment_stats_workspace / ebfi_segment_stats (per-layer weight and gradient statistics of the training monitor),
- *      likewise */
+ *      likewise; and ebfi_optim_step (Adam / AdamW with weight decay and AMSGrad, SGD with momentum: the optimiser section of
+ *      the training config), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -645,6 +647,34 @@ int ebfi_adam_step(float *param, const float *grad, float *exp_avg, float *exp_a
  * of a data-parallel job takes the same branch without a collective of its own for the flag. */
 int ebfi_adam_step_guarded(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *step, int64_t n,
                            double lr, double beta1, double beta2, double eps, int *guard, const float *flag, void *stream);
+
+/* The optimiser section of the training config (the reference: eval(config['optimizer']['name'])(params,
+ * **config['optimizer']['args']), train_ours.py:770-771) as ONE launch over the flat fp32 buffer of n elements, in place.
+ * Hyper-parameters travel by value, so a scheduler's new lr needs no recapture of a graph.  grad is only read.
+ *   kind EBFI_OPTIM_ADAM  torch.optim.Adam / AdamW.  state0 = exp_avg, state1 = exp_avg_sq, state2 = max_exp_avg_sq (read and
+ *        written only with EBFI_OPTIM_AMSGRAD, NULL otherwise), step = device scalar holding the ALREADY incremented count.
+ *        weight_decay != 0: grad' = grad + weight_decay param before the moments (L2, torch.optim.Adam), or with
+ *        EBFI_OPTIM_DECOUPLED_DECAY param <- param (1 - lr weight_decay) before the update (torch.optim.AdamW).
+ *        EBFI_OPTIM_AMSGRAD: max_exp_avg_sq <- max(max_exp_avg_sq, exp_avg_sq), and the denominator is built from it.
+ *        Bias corrections in double precision as in ebfi_adam_step.  momentum / dampening are ignored.  Without weight decay
+ *        and AMSGrad this IS ebfi_adam_step_guarded: the same kernel, the same bits.
+ *   kind EBFI_OPTIM_SGD   torch.optim.SGD.  d = grad + weight_decay param; with momentum != 0 (state0 = momentum_buffer,
+ *        step as above): buf <- d when step[0] == 1 (the first APPLIED step: a skipped step takes the count back),
+ *        buf <- momentum buf + (1 - dampening) d afterwards; d <- d + momentum buf with EBFI_OPTIM_NESTEROV (needs
+ *        momentum > 0 and dampening == 0, as torch does), d <- buf otherwise; param <- param - lr d.  With momentum == 0
+ *        neither state0 nor step is touched (both may be NULL).  beta1 / beta2 / eps, state1 and state2 are ignored.
+ * guard / flag: exactly as in ebfi_adam_step_guarded -- a skipped step writes no parameter and no state element, takes the
+ * step word back, counts in guard[1], and guard[0] becomes 1 when the flag said skip.
+ * A flag of the other kind, or an unknown one, is EBFI_ERR_ARG; an unknown kind EBFI_ERR_UNSUPPORTED.  Every buffer that is
+ * used must be 16-byte aligned.  Bytes moved per launch: 4 n x (3 plain SGD, 5 SGD with momentum, 7 Adam, 9 AMSGrad). */
+#define EBFI_OPTIM_ADAM 0
+#define EBFI_OPTIM_SGD 1
+#define EBFI_OPTIM_DECOUPLED_DECAY 1
+#define EBFI_OPTIM_AMSGRAD 2
+#define EBFI_OPTIM_NESTEROV 4
+int ebfi_optim_step(int kind, int flags, float *param, const float *grad, float *state0, float *state1, float *state2,
+                    float *step, int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                    double momentum, double dampening, int *guard, const float *flag, void *stream);
 
 /* Gradient packing of a training step (replaces the bucket copy of DistributedDataParallel, train_ours.py:754, and the
  * 255-piece concatenation of earlier rounds): `grads` / `numels` are HOST arrays of `count` device pointers (NULL: that
