@@ -4273,6 +4273,134 @@ extern "C" int ebfi_conv2d_backward_weight_f16c_batch(int n, const void *const *
     return check_launch("conv_wgrad_reduce_batch");
 }
 
+// n PURE weight gradients (no activation, fp32 operands), each with its own geometry, in ceil(n / 16) launches of
+// conv_wgrad_f16_tr_multi + conv_wgrad_reduce_multi.  Admitted per item: what ebfi_conv2d_backward_weight_f16g_ex launches as
+// conv_wgrad_f16_tr<ACT_NONE> (3x3, stride 1, pad 1, groups 1, W % 4 == 0, Cin >= 16, 16-byte aligned operands, not a thin
+// layer); one item outside that: EBFI_ERR_UNSUPPORTED for the whole call, before anything is launched.
+namespace {
+// the reductions of conv_wgrad_f16_tr_multi: conv_wgrad_reduce_batch with a slab count per layer; blockIdx.y = layer
+struct ReduceMultiItem {
+    const float *slab;
+    float *gw, *gb;
+    int64_t n_weight, n_total;
+    int perm_cin, nslabs;
+};
+struct ReduceMulti {
+    ReduceMultiItem item[WGRAD_MULTI_MAX];
+};
+__global__ __launch_bounds__(256) void conv_wgrad_reduce_multi(ReduceMulti rb) {
+    const ReduceMultiItem &it = rb.item[blockIdx.y];
+    if ((int64_t)blockIdx.x * 64 >= it.n_total) return;      // (whole workgroup: layers of different sizes share the grid)
+    wgrad_reduce_body(it.slab, it.nslabs, it.n_weight, it.n_total, it.gw, it.gb, it.perm_cin, 9);
+}
+
+int64_t wgrad_multi_tiles(const ConvGeom &g) { return (int64_t)g.B * ceil_div(g.Ho, TRH) * ceil_div(g.Wo, TRW); }
+// Split counts of the items of ONE launch: every item keeps the split count of the one-layer launcher (wgrad_x3_splits, never
+// more than tiles), whatever shares the launch with it.  Its slabs then hold the partial sums of the same tiles in the same
+// order and the reduction adds the same slabs in the same order: the gradients are bit-identical to the per-layer launches.
+// (Sharing ONE resident round of workgroups among the items in proportion to tiles x blocks was measured as well: the queued
+// work of a step in 390 instead of 427 us -- but it reorders the fp32 sums, and Adam turns that 1e-7 into per-tensor differences
+// of tens of percent within 25 steps from the x0.1 initialisation, so a build could no longer be compared with its parent
+// array for array.  profiles/wgrad_multi/README.md.)
+void wgrad_multi_plan(const ConvGeom *g, int n, int *nsplit) {
+    for (int k = 0; k < n; ++k) {
+        const int64_t tiles = wgrad_multi_tiles(g[k]);
+        const int s = wgrad_x3_splits(g[k], 3);
+        nsplit[k] = (int)(s > tiles ? tiles : s);
+    }
+}
+size_t wgrad_multi_slab_bytes(const ConvGeom &g, int nsplit) {
+    const size_t b = (size_t)nsplit * ((size_t)g.Cout * g.Cin * 9 + g.Cout) * sizeof(float);
+    return (b + 255) / 256 * 256;
+}
+}  // namespace
+
+extern "C" size_t ebfi_conv2d_backward_weight_f16g_multi_workspace(int n, const int *B, const int *Cin, const int *H, const int *W,
+                                                                   const int *Cout) {
+    if (n < 1 || !B || !Cin || !H || !W || !Cout) return 0;
+    size_t total = 0;
+    for (int k0 = 0; k0 < n; k0 += WGRAD_MULTI_MAX) {
+        const int m = n - k0 < WGRAD_MULTI_MAX ? n - k0 : WGRAD_MULTI_MAX;
+        ConvGeom g[WGRAD_MULTI_MAX];
+        int ns[WGRAD_MULTI_MAX];
+        for (int k = 0; k < m; ++k)
+            if (B[k0 + k] < 1 || make_geom(g[k], B[k0 + k], Cin[k0 + k], H[k0 + k], W[k0 + k], Cout[k0 + k], 3, 1, 1) != EBFI_OK) return 0;
+        wgrad_multi_plan(g, m, ns);
+        for (int k = 0; k < m; ++k) total += wgrad_multi_slab_bytes(g[k], ns[k]);
+    }
+    return total;
+}
+
+extern "C" int ebfi_conv2d_backward_weight_f16g_multi(int n, const void *const *input, const void *const *grad_output,
+                                                      void *const *grad_weight, void *const *grad_bias, const int *B, const int *Cin,
+                                                      const int *H, const int *W, const int *Cout, const int *ksize, const int *stride,
+                                                      const int *pad, const int *groups, void *const *x_slot, void *const *g_slot,
+                                                      void *workspace, size_t workspace_bytes, void *stream) {
+    if (n < 1) return fail(EBFI_ERR_ARG, "conv2d_backward_weight_f16g_multi: %d layers", n);
+    if (!input || !grad_output || !grad_weight || !grad_bias || !B || !Cin || !H || !W || !Cout || !ksize || !stride || !pad || !groups ||
+        !x_slot || !g_slot)
+        return fail(EBFI_ERR_ARG, "conv2d_backward_weight_f16g_multi: null argument");
+    // every item is checked before the first launch
+    for (int k = 0; k < n; ++k) {
+        if (!input[k] || !grad_output[k] || !grad_weight[k]) return fail(EBFI_ERR_ARG, "conv2d_backward_weight_f16g_multi: null argument (layer %d)", k);
+        if (ksize[k] != 3 || stride[k] != 1 || pad[k] != 1 || groups[k] != 1 || B[k] < 1 || Cin[k] < 16 || W[k] % 4 != 0 ||
+            !aligned16(input[k]) || !aligned16(grad_output[k]))
+            return fail(EBFI_ERR_UNSUPPORTED, "conv2d_backward_weight_f16g_multi: layer %d (k=%d stride %d pad %d, %d groups, %d -> %d channels, "
+                                              "W=%d) is not a 3x3 same-padded stride-1 layer on quad-aligned rows with >= 16 input channels and "
+                                              "16-byte aligned operands", k, ksize[k], stride[k], pad[k], groups[k], Cin[k], Cout[k], W[k]);
+        ConvGeom g;
+        if (int rc = make_geom(g, B[k], Cin[k], H[k], W[k], Cout[k], 3, 1, 1)) return rc;
+        if (shift_wgrad_geometry(g, 3, 1).kind != 0 || thin_wgrad_geometry(g, 3, 1).kind != 0)
+            return fail(EBFI_ERR_UNSUPPORTED, "conv2d_backward_weight_f16g_multi: layer %d (%d -> %d) is a thin layer with kernels of its own", k,
+                        Cin[k], Cout[k]);
+        if (wgrad_multi_tiles(g) > 2147483647LL / 4) return fail(EBFI_ERR_ARG, "conv2d_backward_weight_f16g_multi: too many tiles (layer %d)", k);
+    }
+    const size_t need = ebfi_conv2d_backward_weight_f16g_multi_workspace(n, B, Cin, H, W, Cout);
+    if (!workspace || workspace_bytes < need)
+        return fail(EBFI_ERR_WORKSPACE, "conv2d_backward_weight_f16g_multi: workspace %zu bytes < required %zu", workspace_bytes, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace);
+    for (int k0 = 0; k0 < n; k0 += WGRAD_MULTI_MAX) {
+        const int m = n - k0 < WGRAD_MULTI_MAX ? n - k0 : WGRAD_MULTI_MAX;
+        ConvGeom g[WGRAD_MULTI_MAX];
+        int ns[WGRAD_MULTI_MAX];
+        for (int k = 0; k < m; ++k) (void)make_geom(g[k], B[k0 + k], Cin[k0 + k], H[k0 + k], W[k0 + k], Cout[k0 + k], 3, 1, 1);
+        wgrad_multi_plan(g, m, ns);
+        WgradMulti mt{};
+        ReduceMulti rb{};
+        double flops = 0.0, bytes = 0.0;
+        int64_t wgs = 0, n_total_max = 0;
+        for (int k = 0; k < m; ++k) {
+            const int i = k0 + k;
+            const int64_t n_weight = (int64_t)g[k].Cout * g[k].Cin * 9, n_total = n_weight + g[k].Cout;
+            float *slab = reinterpret_cast<float *>(ws);
+            ws += wgrad_multi_slab_bytes(g[k], ns[k]);
+            mt.item[k] = WgradMultiItem{static_cast<const float *>(input[i]), static_cast<const float *>(grad_output[i]), slab,
+                                        static_cast<float *>(x_slot[i]), static_cast<float *>(g_slot[i]), g[k].B, g[k].Cin, g[k].H, g[k].W,
+                                        g[k].Cout, ns[k], (int)wgrad_multi_tiles(g[k]), grad_bias[i] != nullptr ? 1 : 0, (int)wgs, 0};
+            rb.item[k] = ReduceMultiItem{slab, static_cast<float *>(grad_weight[i]), static_cast<float *>(grad_bias[i]), n_weight, n_total,
+                                         g[k].Cin, ns[k]};
+            wgs += ceil_div((int64_t)ns[k] * ceil_div(g[k].Cout, 64) * ceil_div(g[k].Cin, 64), 8) * 8;   // (first ids: multiples of 8)
+            n_total_max = n_total > n_total_max ? n_total : n_total_max;
+            flops += 2.0 * g[k].B * g[k].Ho * g[k].Wo * (double)g[k].Cout * g[k].Cin * 9;
+            bytes += conv_bytes_wgrad(g[k], 9, false, false);
+        }
+        if (wgs > 2147483647LL) return fail(EBFI_ERR_ARG, "conv2d_backward_weight_f16g_multi: too many workgroups");
+        {
+            ProfScope ps("conv_wgrad_f16_tr/f32_multi", st, flops, bytes);
+            if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_wgrad_f16_tr_multi), TR_LDS + KB_LDS_BYTES)) return rc_;
+            hipLaunchKernelGGL(conv_wgrad_f16_tr_multi, dim3((unsigned)wgs), dim3(512), TR_LDS + KB_LDS_BYTES, st, mt, m);
+            if (int rc = check_launch("conv_wgrad_f16_tr_multi")) return rc;
+        }
+        {
+            ProfScope ps("conv_wgrad_reduce_f32", st);
+            hipLaunchKernelGGL(conv_wgrad_reduce_multi, dim3((unsigned)ceil_div(n_total_max, 64), (unsigned)m), dim3(256), 0, st, rb);
+            if (int rc = check_launch("conv_wgrad_reduce_multi")) return rc;
+        }
+    }
+    return EBFI_OK;
+}
+
 extern "C" int ebfi_f16_scales_finish(void *slots, int n, void *flag, void *stream) {
     if (!slots || !flag || n < 0) return fail(EBFI_ERR_ARG, "f16_scales_finish: bad argument");
     if (n == 0) return EBFI_OK;

@@ -1414,3 +1414,53 @@ __global__ __launch_bounds__(512) void conv_wgrad_f16_tr_batch(WgradBatch bt, Co
                                          false, it.need_bias, ScaleSlot{it.x_slot}, ScaleSlot{it.g_slot}, two_co ? which : 0,
                                          two_co ? 0 : which);
 }
+
+// Several PURE weight gradients (fp32 operands, no activation folded), each with a geometry of its own, in one launch: the
+// detail branch's layers, whose gradients nothing in the backward pass waits for, queued over the step and run together
+// (ebfi_amd/wgradqueue.py).  Alone, each of them is a launch of its own that fills the chip for a few microseconds -- a
+// 128 -> 128 layer at 32 x 32 is 64 splits of ONE tile -- with the start-up, the drain and the launch gap paid per layer.  Together
+// the workgroups of all layers are dispatched back to back: every item keeps its split count (wgrad_multi_plan), so its slabs,
+// and the gradients reduced from them, are bit for bit those of the one-layer launch.
+// The items travel BY VALUE in the kernel arguments (the launch is a node of a captured graph: no descriptor table in device
+// memory).  Workgroup -> item by a scalar walk over the items' first workgroup ids (multiples of 8, so that L & 7 below is the XCD
+// as in the one-layer launch), then (split, co block, ci block) exactly as conv_wgrad_f16_tr places them.
+struct WgradMultiItem {
+    const float *x, *gout;
+    float *slab, *x_slot, *g_slot;
+    int B, Cin, H, W, Cout;
+    int nsplit, total_tiles, need_bias;
+    int wg_begin, pad_;
+};
+constexpr int WGRAD_MULTI_MAX = 16;
+struct WgradMulti {
+    WgradMultiItem item[WGRAD_MULTI_MAX];
+};
+__global__ __launch_bounds__(512) void conv_wgrad_f16_tr_multi(WgradMulti mt, int n) {
+    int k = 0;
+    for (int j = 1; j < n; ++j)
+        if ((int)blockIdx.x >= mt.item[j].wg_begin) k = j;
+    const WgradMultiItem &it = mt.item[k];
+    const int nx = it.nsplit, ny = (it.Cout + 63) / 64, nz = (it.Cin + 63) / 64;
+    const int L = (int)blockIdx.x - it.wg_begin, total = nx * ny * nz;
+    if (L >= total) return;                                  // (the padding up to the next item's first id: whole workgroup, before any barrier)
+    int split, co_blk, ci_blk;
+    {
+        const int T8 = total / (8 * nz) * (8 * nz);
+        int rest;
+        if (L < T8) {
+            const int xcd = L & 7, i = L >> 3;
+            ci_blk = i % nz;
+            rest = (i / nz) * 8 + xcd;
+        } else {
+            ci_blk = (L - T8) % nz;
+            rest = T8 / nz + (L - T8) / nz;
+        }
+        split = rest % nx;
+        co_blk = rest / nx;
+    }
+    ConvGeom g{it.B, it.Cin, it.H, it.W, it.Cout, it.H, it.W, 1};
+    const int64_t wsz = (int64_t)g.Cout * g.Cin * 9;
+    wgrad_tr_body<ACT_NONE, false, false>(it.x, it.gout, nullptr, nullptr, it.slab + (int64_t)split * (wsz + g.Cout), g, 0.f, split, nx,
+                                          it.total_tiles, (nx & 7) == 0, it.need_bias, ScaleSlot{it.x_slot}, ScaleSlot{it.g_slot},
+                                          co_blk, ci_blk, 0);
+}

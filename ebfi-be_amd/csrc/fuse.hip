@@ -103,6 +103,38 @@ __global__ void gather_sum_kernel(const float *__restrict__ src, const int *__re
     out[i] = acc;
 }
 
+// Several gathers in one launch (the fold gathers of a training step's weight gradients, queued by ebfi_amd/wgradqueue.py): the
+// items travel by value in the kernel arguments, a workgroup finds its item by a scalar walk over the items' first workgroup
+// ids.  Per output element the additions of gather_sum_kernel in the same order: the same bits.
+struct GatherItem {
+    const float *src;
+    const int *idx;
+    float *out;
+    int64_t n_out;
+    int R, wg_begin;
+};
+constexpr int GATHER_MULTI_MAX = 48;
+struct GatherMulti {
+    GatherItem item[GATHER_MULTI_MAX];
+};
+__global__ __launch_bounds__(256) void gather_sum_multi_kernel(GatherMulti gm, int n) {
+    int k = 0;
+    for (int j = 1; j < n; ++j)
+        if ((int)blockIdx.x >= gm.item[j].wg_begin) k = j;
+    const GatherItem &it = gm.item[k];
+    const int64_t i = (int64_t)((int)blockIdx.x - it.wg_begin) * 256 + threadIdx.x;
+    if (i >= it.n_out) return;
+    const int R = it.R;
+    const int *__restrict__ idx = it.idx;
+    const float *__restrict__ src = it.src;
+    float acc = 0.f;
+    for (int r = 0; r < R; ++r) {
+        const int j = idx[i * R + r];
+        if (j >= 0) acc += src[j];
+    }
+    it.out[i] = acc;
+}
+
 // product-mean: out[plane] = mean_i a[plane][i] * b[plane][i]   (AdaptiveAvgPool2d(1) of a product of two maps:
 // ExposureDecision's correlation of the normalised event / blur features, model_singleframe.py:66-68) and its adjoint
 // ga = (g[plane] / n) * b, gb = (g[plane] / n) * a.  One workgroup per plane, fixed-order reduction.
@@ -613,6 +645,38 @@ extern "C" int ebfi_gather_sum(const float *src, const int32_t *idx, float *out,
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(gather_sum_kernel, dim3((unsigned)ceil_div(n_out, 256)), dim3(256), 0, st, src, idx, out, n_out, R);
     return check_launch("gather_sum");
+}
+
+// n gathers (arrays of n entries) in ceil(n / 48) launches: the same bits as n calls of ebfi_gather_sum
+extern "C" int ebfi_gather_sum_multi(int n, const float *const *src, const int32_t *const *idx, float *const *out, const int64_t *n_out,
+                                     const int *R, void *stream) {
+    if (n < 0 || !src || !idx || !out || !n_out || !R) return fail(EBFI_ERR_ARG, "gather_sum_multi: bad argument");
+    for (int k = 0; k < n; ++k) {
+        if (!src[k] || !idx[k] || !out[k]) return fail(EBFI_ERR_ARG, "gather_sum_multi: null argument (item %d)", k);
+        if (n_out[k] < 0 || R[k] <= 0) return fail(EBFI_ERR_ARG, "gather_sum_multi: bad dimensions (item %d)", k);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int k = 0;
+    while (k < n) {
+        GatherMulti gm{};
+        int m = 0;
+        int64_t wgs = 0;
+        for (; k < n && m < GATHER_MULTI_MAX; ++k) {
+            if (n_out[k] == 0) continue;
+            const int64_t w = ceil_div(n_out[k], 256);
+            if (wgs + w > 2147483647LL) {
+                if (m == 0) return fail(EBFI_ERR_ARG, "gather_sum_multi: item %d is too large", k);
+                break;                                   // (the next launch takes it)
+            }
+            gm.item[m++] = GatherItem{src[k], idx[k], out[k], n_out[k], R[k], (int)wgs};
+            wgs += w;
+        }
+        if (m == 0) break;
+        ProfScope ps("gather_sum", st);
+        hipLaunchKernelGGL(gather_sum_multi_kernel, dim3((unsigned)wgs), dim3(256), 0, st, gm, m);
+        if (int rc = check_launch("gather_sum_multi")) return rc;
+    }
+    return EBFI_OK;
 }
 
 // out[planes] = mean over HW of a*b (a, b [planes, HW] contiguous); HW a multiple of 4

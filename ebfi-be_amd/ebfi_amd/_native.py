@@ -84,6 +84,8 @@ SIGNATURES = {
     "ebfi_conv2d_backward_weight_f16c": (_i, [_vp, _vp, _i, _vp, _vp] + [_i] * 6 + [_vp, _vp, _vp, _sz, _vp]),
     "ebfi_conv2d_backward_weight_f16c_batch_workspace": (_sz, [_i, _vp, _vp]),
     "ebfi_conv2d_backward_weight_f16c_batch": (_i, [_i] + [_vp] * 9 + [_i, _i, _i, _vp, _sz, _vp]),
+    "ebfi_conv2d_backward_weight_f16g_multi_workspace": (_sz, [_i] + [_vp] * 5),
+    "ebfi_conv2d_backward_weight_f16g_multi": (_i, [_i] + [_vp] * 15 + [_vp, _sz, _vp]),
     "ebfi_fac_forward_p16": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ebfi_fac_backward_p16": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_float, _i, _i, _i, _i, _i, _vp]),
     "ebfi_scale_residual_cat_forward_c16": (_i, [_vp] * 8 + [_i, _i, _i, _i, _i64, _vp]),
@@ -109,6 +111,7 @@ SIGNATURES = {
     "ebfi_prodmean_forward": (_i, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "ebfi_prodmean_backward": (_i, [_vp] * 5 + [_i64, _i64, _vp]),
     "ebfi_gather_sum": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
+    "ebfi_gather_sum_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ebfi_se_gate_workspace": (_c.c_size_t, [_i, _i, _i64]),
     "ebfi_se_gate_forward": (_i, [_vp] * 8 + [_i, _i, _i64, _i, _c.c_float, _vp]),
     "ebfi_se_gate_backward": (_i, [_vp] * 11 + [_i, _i, _i64, _i, _c.c_float, _vp]),

@@ -255,7 +255,7 @@ class SiteConvBiasAct(Function):
         N.check(rc, "ebfi_conv2d_forward_bf16x3 (packed)")
         if grad_preact:                      # the incoming gradient is already that of the pre-activation
             act, slope = ACT_NONE, 0.0
-        ctx.site, ctx.cfg, ctx.geo = site, (act, slope), geo
+        ctx.site, ctx.cfg, ctx.geo, ctx.params = site, (act, slope), geo, params
         ctx.save_for_backward(x, out if act != ACT_NONE else None)
         return out
 
@@ -263,16 +263,20 @@ class SiteConvBiasAct(Function):
     def backward(ctx, gout):
         x, y = ctx.saved_tensors
         site, (act, slope), geo = ctx.site, ctx.cfg, ctx.geo
-        gx, pgrads = _site_backward(site, geo, act, slope, x, y, gout, ctx.needs_input_grad[0], any(ctx.needs_input_grad[6:]))
+        gx, pgrads = _site_backward(site, geo, act, slope, x, y, gout, ctx.needs_input_grad[0], any(ctx.needs_input_grad[6:]),
+                                    params=(ctx.params, ctx.needs_input_grad[6:]))
         return (gx, None, None, None, None, None) + tuple(pgrads)
 
 
-def _site_backward(site, geo, act, slope, x, y, gout, need_x, need_p, unshuffle=None):
+def _site_backward(site, geo, act, slope, x, y, gout, need_x, need_p, unshuffle=None, params=None):
     """Backward of one bank-site convolution (SiteConvBiasAct): returns (grad_x or None, [gradients of the site's source weights, then
     of its source biases]).  unshuffle = (mask, mask_slope): the layer's input came out of PixelShuffle(2) + LeakyReLU(mask_slope)
     behind another convolution (mask = that input, `x`): grad_x leaves as the PRE-activation gradient of that convolution, in its
     layout [B, 4*Cin, H/2, W/2] -- the data-gradient kernel applies LeakyReLU'(mask) and stores through the inverse shuffle
-    (ebfi_conv2d_packed_f16_shuffled), so neither the pixel-unshuffle copy nor a mask pass over the saved activation runs."""
+    (ebfi_conv2d_packed_f16_shuffled), so neither the pixel-unshuffle copy nor a mask pass over the saved activation runs.
+    params = (the site's source parameters, which of them need a gradient): inside a wgradqueue scope the weight-gradient work
+    that nothing here waits for is queued on it -- the whole launch of a pure layer (act none), the fold gathers of any folded
+    site -- and the gradients it will assign come back as None."""
     gout = gout.contiguous()
     lib = N.lib()
     gx, pgrads = None, [None] * (len(site.w_shapes) + len(site.b_shapes))
@@ -290,6 +294,8 @@ def _site_backward(site, geo, act, slope, x, y, gout, need_x, need_p, unshuffle=
     f16_w = f16 and (Cin % 64 == 0 or (Cin >= 32 and W % 4 == 0 and al16))
     f16_x = f16 and W % 4 == 0 and Cin >= 48 and site.tr16_ptr() is not None
     gpre = None
+    from . import wgradqueue
+    queue = wgradqueue.active() if params is not None and need_p and wgradqueue.deferrable(*params) else None
 
     def weight_gradients(st_w):
         """weight / bias gradient launches (+ slab reduction, + fold gathers) on stream `st_w`; returns (pgrads, gpre)."""
@@ -316,11 +322,17 @@ def _site_backward(site, geo, act, slope, x, y, gout, need_x, need_p, unshuffle=
             rc = lib.ebfi_conv2d_backward_weight_ex(N.ptr(x), N.ptr(gout), N.ptr(y), N.ptr(gw2), N.ptr(gb2), N.ptr(gp), *geo,
                                                     act, slope, N.ptr(ws), need, N.EBFI_F32_BF16X3MMA, st_w)
         N.check(rc, "ebfi_conv2d_backward_weight")
+        if queue is not None and site.kind != "id":          # (the fold gathers wait for the flush)
+            queue.add_routes(site, gw2, gb2, *params)
+            return pgrads, gp
         return _route_site_grads(site, gw2, gb2, st_w), gp
 
     with torch.cuda.device_of(x):
         st = N.stream_ptr(x.device)
-        if need_p:
+        if need_p and queue is not None and f16_w and wgradqueue.eligible(site, geo, act, x, gout):
+            # (slot pointers, and a first-use calibration, now: the operands are what they are at this point of the pass)
+            queue.add_layer(site, x, gout, geo, book.operand((site.key, "x"), x), book.operand((site.key, "g"), gout), *params)
+        elif need_p:
             pgrads, gpre = weight_gradients(st)
         if need_x:
             src, sy, a = (gpre, None, ACT_NONE) if gpre is not None else (gout, y, act)
@@ -387,6 +399,7 @@ class SiteConvShufflePair(Function):
                                                     site_b.fwd_ptr(), site_b.fwd_bytes, st)
             N.check(rc, "ebfi_conv2d_forward_bf16x3 (packed)")
         ctx.sites, ctx.cfg, ctx.geos, ctx.na = (site_a, site_b), (slope_a, act_b, slope_b), (geo_a, geo_b), na
+        ctx.params = params
         ctx.save_for_backward(x, y1, y2 if act_b != ACT_NONE else None)
         return y2
 
@@ -397,10 +410,12 @@ class SiteConvShufflePair(Function):
         need = ctx.needs_input_grad
         need_pa, need_pb = any(need[7:7 + na]), any(need[7 + na:])
         need_a = need[0] or need_pa
-        ga, pg_b = _site_backward(site_b, geo_b, act_b, slope_b, y1, y2, g2, need_a, need_pb, unshuffle=(y1, slope_a))
+        ga, pg_b = _site_backward(site_b, geo_b, act_b, slope_b, y1, y2, g2, need_a, need_pb, unshuffle=(y1, slope_a),
+                                  params=(ctx.params[na:], need[7 + na:]))
         gx, pg_a = (None, [None] * na)
         if need_a:                               # (A's activation derivative is already in ga)
-            gx, pg_a = _site_backward(site_a, geo_a, ACT_NONE, 0.0, x, None, ga, need[0], need_pa)
+            gx, pg_a = _site_backward(site_a, geo_a, ACT_NONE, 0.0, x, None, ga, need[0], need_pa,
+                                      params=(ctx.params[:na], need[7:7 + na]))
         return (gx, None, None, None, None, None, None) + tuple(pg_a) + tuple(pg_b)
 
 

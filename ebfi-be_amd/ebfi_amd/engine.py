@@ -85,7 +85,7 @@ def synthetic_validation_batch(B, H, W, TB=16, num_frames=4, device="cuda", seed
 class Engine(graphstep.GraphStepper):
     def __init__(self, model_args=None, device="cuda", precision="fp32", lr=1e-4, seed=None, train=True, graph=False,
                  accu_step=1, betas=(0.9, 0.999), backward_f16=None, forward_f16="filters", strict_graph=None,
-                 perceptual=None, optimizer=None):
+                 perceptual=None, optimizer=None, defer_wgrad=True, defer_wgrad_cap=None):
         """graph / accu_step / strict_graph: see graphstep.GraphStepper (a graph is captured per input shape, precision and loss
         phase).
         optimizer: None = Adam with `lr` / `betas` (the shipped config), or the config's optimizer section {"name": "Adam" |
@@ -105,7 +105,11 @@ class Engine(graphstep.GraphStepper):
         backward_f16 (training, precision 'bf16x3' only; default on): the data / weight gradients of the 3x3 layers run ONE
         fp16 MFMA per product with delayed power-of-two operand scales (ebfi_amd.f16scale) instead of three bf16 ones; the
         forward pass keeps the split-precision kernels.  Gradient parity is unchanged (tests/test_gpu_model.py:
-        test_benchmarked_step_vs_oracle); False restores the split-precision backward."""
+        test_benchmarked_step_vs_oracle); False restores the split-precision backward.
+        defer_wgrad (with the fp16 backward; default on): the pure weight gradients of the small layers and the fold gathers of
+        the detail branch are queued over the backward pass and run in a few batched launches behind it (ebfi_amd.wgradqueue);
+        False launches them layer by layer where autograd meets them.  defer_wgrad_cap: bytes of queued operands that force an
+        early flush (None: wgradqueue.BYTE_CAP)."""
         if precision not in ("fp32", "bf16x3", "bf16"):
             raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
         super().__init__(device, graph=graph, accu_step=accu_step, strict_graph=strict_graph)
@@ -120,6 +124,7 @@ class Engine(graphstep.GraphStepper):
         # moves by lr) lifts them to 1e-4 -- fourteen decades in one step, which no one-step-old scale survives.  From the
         # third step on magnitudes move by a few percent per step and the delayed scales (f16scale) take over.
         self.calibration_steps = 2
+        self.defer_wgrad, self.defer_wgrad_cap = bool(defer_wgrad), defer_wgrad_cap
         self.perceptual = perceptual if train else None
         # ebfi_amd.monitor (images on): sample 0 of the restored frame of every pass is kept in `panel_sharp` -- one small copy inside
         # the (captured) step -- and `validate` leaves (Frame, Event, last Final, last LatentF) in `last_valid_panels`.  Off by
@@ -168,7 +173,10 @@ class Engine(graphstep.GraphStepper):
         return self.book.active()
 
     def _fwd_bwd(self, frame, event, t, gtex, target):
-        with self._autocast(), self._bank(), self._book() as book:
+        from . import wgradqueue
+        cap = wgradqueue.BYTE_CAP if self.defer_wgrad_cap is None else self.defer_wgrad_cap
+        with self._autocast(), self._bank(), self._book() as book, \
+                wgradqueue.scope(self.defer_wgrad and self.book is not None, cap) as queue:
             if book is not None and self._steps_run < self.calibration_steps:
                 book.calibrated.clear()             # (measure every operand of this pass again, see __init__)
             sharp_pre, sharp = self.model(frame, event, t, gtex)
@@ -180,6 +188,8 @@ class Engine(graphstep.GraphStepper):
             if self.perceptual is not None:
                 loss = loss + self.perceptual(sharp.float(), target) / self.accu_step
             loss.backward()
+            if queue is not None:
+                queue.flush()                       # (before the finish: its launches record operand maxima the finish reads)
             if book is not None:
                 book.finish()                       # next step's operand scales from this pass's maxima; guard on overflow
         return loss.detach()

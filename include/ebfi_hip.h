@@ -103,7 +103,9 @@ extern "C" {
  *      ebfi_lpips_vgg_train_workspace / ebfi_lpips_vgg_forward_train / ebfi_lpips_vgg_backward (the same as a training loss); and
  *      ebfi_segment_stats_workspace / ebfi_segment_stats (per-layer weight and gradient statistics of the training monitor),
  *      likewise; and ebfi_optim_step (Adam / AdamW with weight decay and AMSGrad, SGD with momentum: the optimiser section of
- *      the training config), likewise */
+ *      the training config), likewise; and ebfi_conv2d_backward_weight_f16g_multi_workspace /
+ *      ebfi_conv2d_backward_weight_f16g_multi (the pure weight gradients of a training step, deferred and run in one launch) and
+ *      ebfi_gather_sum_multi (their fold gathers), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -416,6 +418,21 @@ int ebfi_conv2d_backward_weight_f16c_batch(int n, const void *const *input16, co
                                            void *const *grad_bias, const int *Cin_per_group, const int *Cout, const int *groups,
                                            void *const *x_slot, void *const *g_slot, int B, int H, int W, void *workspace,
                                            size_t workspace_bytes, void *stream);
+/* n weight / bias gradients with a geometry of their own each, in ceil(n / 16) launches (+ as many reduction launches):
+ * the PURE weight gradients of a training step -- fp32 `input` / `grad_output`, the incoming gradient already that of the
+ * pre-activation -- which nothing in the backward pass waits for, deferred to its end (ebfi_amd/wgradqueue.py).  Arguments are
+ * arrays of n entries.  Every item must be what ebfi_conv2d_backward_weight_f16g_ex runs on its pixel-major kernel with act = 0:
+ * ksize 3, stride 1, pad 1, groups 1, W % 4 == 0, Cin >= 16, 16-byte aligned input and grad_output, Cout > 4 on large maps (the
+ * thin layers have kernels of their own); one item outside that returns EBFI_ERR_UNSUPPORTED for the whole call and launches
+ * nothing.  x_slot / g_slot as there (scale applied and |max| recorded while staging; NULL = unscaled); grad_bias entries may be
+ * NULL.  Every item keeps the split count of ebfi_conv2d_backward_weight_f16g_ex, whatever shares the launch with it: each
+ * result is bit-identical to that entry point's.  Deterministic. */
+size_t ebfi_conv2d_backward_weight_f16g_multi_workspace(int n, const int *B, const int *Cin, const int *H, const int *W, const int *Cout);
+int ebfi_conv2d_backward_weight_f16g_multi(int n, const void *const *input, const void *const *grad_output, void *const *grad_weight,
+                                           void *const *grad_bias, const int *B, const int *Cin, const int *H, const int *W,
+                                           const int *Cout, const int *ksize, const int *stride, const int *pad, const int *groups,
+                                           void *const *x_slot, void *const *g_slot, void *workspace, size_t workspace_bytes,
+                                           void *stream);
 /* The 1600-channel tensors of the KernelConv -> FAC pair in the TRAINING step (reference
  * models/Ours/model_singleframe.py:161-162, KernelConv2D_kernel.cu:25-150): the filters and grad_kernel as PLANAR fp16
  * [B, C*K*K, Ho, Wo] scaled by a slot's power of two -- the layout the FAC kernels stream plane by plane.  The 128 -> 1600
@@ -523,6 +540,9 @@ int ebfi_prodmean_backward(const float *a, const float *b, const float *grad_out
  * re-layouts that turn the depth-2 Conv3d / ConvTranspose3d of the detail branch (models/model_misc/resnet_3D.py,
  * model_singleframe.py:170-223) into 2-D convolutions, and their adjoints. */
 int ebfi_gather_sum(const float *src, const int32_t *idx, float *out, int64_t n_out, int R, void *stream);
+/* n of them (arrays of n entries) in ceil(n / 48) launches; bit-identical to n calls of ebfi_gather_sum. */
+int ebfi_gather_sum_multi(int n, const float *const *src, const int32_t *const *idx, float *const *out, const int64_t *n_out,
+                          const int *R, void *stream);
 
 /* ------------------------------------------------------------------ squeeze-excite gate of the detail branch
  * SEGating (models/model_misc/resnet_3D.py:89-105) fused with what follows it: out = act(x * sigmoid(W mean(x) + b) (+ res)).
