@@ -164,6 +164,8 @@ SIGNATURES = {
     "ebfi_frames_u8_to_planar": (_i, [_vp, _p64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ebfi_planar_to_u8": (_i, [_vp, _p64, _i64, _i, _i, _vp, _vp]),
     "ebfi_period_frames_u8": (_i, [_vp, _p64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ebfi_event_augment": (_i, [_vp, _p64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _c.c_uint64, _vp, _i, _i64, _vp, _vp]),
+    "ebfi_event_hot_pixels": (_i, [_vp, _i64, _i, _i, _c.c_uint64, _vp, _i, _i64, _vp]),
     "ebfi_event_cnt_image_workspace": (_i64, [_i64, _i, _i, _i]),
     "ebfi_event_cnt_image": (_i, [_vp, _p64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "ebfi_segment_stats_workspace": (_i64, [_i64, _i]),

@@ -139,6 +139,25 @@ def crop_window(h, w, size, mode, scale=1, seed=None):
     return i // scale, j // scale, th // scale, tw // scale
 
 
+def noise_law(noise_mode, noise, hot_pixels):
+    """The `noise_mode` / `hot_pixels` arguments of the datasets, checked -> (noise table or None, hot_pixels or None).
+    "host" is the reference's draw (`draw_noise`); "device" the counter-based law of ebfi_amd.eventaug, whose table is made
+    here once (an empty one when there is no noise: the kernel then only cuts and flips)."""
+    if noise_mode not in ("host", "device"):
+        raise ValueError("noise_mode must be 'host' or 'device', got %r" % (noise_mode,))
+    if hot_pixels is not None:
+        if noise_mode != "device":
+            raise ValueError("hot_pixels come with the device noise law: pass noise_mode='device' (the reference's host law "
+                             "never adds any, h5dataset.py:436)")
+        hot_pixels = (float(hot_pixels[0]), float(hot_pixels[1]))
+    if noise_mode == "host":
+        return None, None
+    from .eventaug import noise_table
+    if hot_pixels is not None:
+        noise_table(hot_pixels[0], 1.0)          # (refuses a bad std now, not at the first item)
+    return (noise_table(*noise) if noise is not None else ()), hot_pixels
+
+
 # ------------------------------------------------------------------------------------------------ storage
 class _NpzClip:
     def __init__(self, path):
@@ -229,18 +248,24 @@ class ClipDataset:
     and one kernel (ebfi_amd.frameio.period_to_planar) writes the sharp planes and the blurry mean with the channel reversal,
     the window and the flips folded into the read -- the same bits, at one byte per sample across the bus.
 
+    noise_mode="device": crop, flips and noise of the event stack are one kernel of `finish` (ebfi_amd.eventaug: a counter-based
+    law with the host draw's distribution, not its bits) and `prepare` draws nothing; hot_pixels=(std, fraction) then adds
+    AugmentData's hot pixels with the item's seed + 4.
+
     An item is made in two halves: `prepare` is host work only (file reads, the staging buffer, the event list, the noise
-    draw) and may run on a worker thread (`batches(..., prefetch=k)`); `finish` issues the uploads and kernels on the calling
+    draw of the host law) and may run on a worker thread (`batches(..., prefetch=k)`); `finish` issues the uploads and kernels on the calling
     thread's current stream.  `__getitem__(i, seed)` is `finish(prepare(i, seed))`."""
 
     def __init__(self, paths, time_bins=16, frames_per_period=16, frames_per_blurry=16, exposure_method="Fixed",
                  exposure_time=None, crop=None, crop_mode="random", flips=False, device="cuda", seed=0,
-                 flip_probs=(0.5, 0.5), center_crop=None, noise=None, frames="host"):
+                 flip_probs=(0.5, 0.5), center_crop=None, noise=None, frames="host", noise_mode="host", hot_pixels=None):
         """crop / crop_mode: the first crop of AugmentData's list (RandomCrop when enabled, else CenterCrop); center_crop: a
         CenterCrop applied AFTER a random crop when the config enables both (the reference walks its `augment` list in order,
         h5dataset.py:410-433); flip_probs: (horizontal_prob, vertical_prob) of data_augment.flip; noise: None or
         (noise_std, noise_fraction) of data_augment.noise -- applied to the event stack after crops and flips with the item's
-        seed + 3, like AugmentData does ('Noise' sits behind the crops and flips in the shipped `augment` order)."""
+        seed + 3, like AugmentData does ('Noise' sits behind the crops and flips in the shipped `augment` order); noise_mode:
+        "host" draws it as the reference does, "device" on the GPU (class docstring); hot_pixels: None or (hot_pixel_std,
+        hot_pixel_fraction) of data_augment.hot_pixel, with noise_mode="device" only."""
         self.clips = [open_clip(p) for p in (list_clips(paths) if isinstance(paths, str) else list(paths))]
         if not self.clips:
             raise ValueError("no clips under %r" % (paths,))
@@ -252,6 +277,8 @@ class ClipDataset:
         if frames not in ("host", "device"):
             raise ValueError("frames must be 'host' or 'device', got %r" % (frames,))
         self.frames = frames
+        self.noise_mode = noise_mode
+        self.noise_table, self.hot_pixels = noise_law(noise_mode, self.noise, hot_pixels)
         self.items = []
         for ci, clip in enumerate(self.clips):
             for it in period_items(clip.num_imgs, frames_per_period, frames_per_blurry, exposure_method, exposure_time, seed + ci):
@@ -357,7 +384,7 @@ class ClipDataset:
         else:
             sharp, blur, events, _ = self.host_item(index)
             prepared.update(sharp=sharp, blur=blur, events=events)
-        if self.noise is not None:          # (drawn over [L=1, TB, 2, h, w] like the reference)
+        if self.noise is not None and self.noise_mode == "host":          # (drawn over [L=1, TB, 2, h, w] like the reference)
             prepared["noise"] = draw_noise((1, self.time_bins, 2) + tuple(self.window(res, seed)[2:]), seed + 3, *self.noise)
         return prepared
 
@@ -375,9 +402,17 @@ class ClipDataset:
             fh, fv = self.flip_decisions(seed)
             sharp, blur = period_to_planar(prepared["stage"].to(dev, non_blocking=True), prepared["num_blur"],
                                            window=(0, j, h, w), reverse_channels=True, flip_h=fh, flip_v=fv)
-            stack, = self.augment([stack], res, seed)
-        else:
+            if self.noise_mode == "host":
+                stack, = self.augment([stack], res, seed)
+        elif self.noise_mode == "host":
             sharp, blur, stack = self.augment([prepared["sharp"].to(dev), prepared["blur"].to(dev), stack], res, seed)
+        else:
+            sharp, blur = self.augment([prepared["sharp"].to(dev), prepared["blur"].to(dev)], res, seed)
+        if self.noise_mode == "device":          # window, flips and noise in one launch; the hot pixels in place behind it
+            from .eventaug import add_hot_pixels, augment_events
+            stack = augment_events(stack, self.window(res, seed), *self.flip_decisions(seed), seed + 3, self.noise_table)
+            if self.hot_pixels is not None:
+                add_hot_pixels(stack, seed + 4, *self.hot_pixels)
         if "noise" in prepared:
             stack = (stack[None] + prepared["noise"].to(dev))[0]
         return self.assemble(sharp, blur, stack, prepared["duty"])
@@ -399,11 +434,14 @@ class RealBlurClipDataset:
     The frame is the stored array WITHOUT channel reversal (GetFrames, :178-189, does not swap, unlike the synthetic-blur
     reader).  It goes to the device as uint8 and becomes planar float there (ebfi_amd.frameio.frames_to_planar), the centre
     crop's window handed to the kernel; the event stack is binned on the device and cropped as in ClipDataset.  Event noise is
-    drawn once per item over the whole [L, TB, 2, H, W] stack with the item's seed + 3, as AugmentData does there."""
+    drawn once per item over the whole [L, TB, 2, H, W] stack with the item's seed + 3, as AugmentData does there; with
+    noise_mode="device" by the device law (ebfi_amd.eventaug), one launch per load cutting the window and adding the load's part
+    of the item's noise field, and hot_pixels=(std, fraction) then adds hot pixels with the item's seed + 4."""
 
     def __init__(self, path, time_bins=16, interp_num=16, periods_per_seq=2, sliding_window_seq=2, periods_per_load=1,
-                 sliding_window_load=1, crop=None, noise=None, device="cuda"):
-        """crop: the CenterCrop size or None; noise: None or (noise_std, noise_fraction) of data_augment.noise."""
+                 sliding_window_load=1, crop=None, noise=None, device="cuda", noise_mode="host", hot_pixels=None):
+        """crop: the CenterCrop size or None; noise: None or (noise_std, noise_fraction) of data_augment.noise; noise_mode /
+        hot_pixels: as for ClipDataset."""
         self.clip = open_clip(path) if isinstance(path, str) else path
         if not self.clip.has_exposure():
             raise ValueError("%s: a real-blur clip needs the per-frame stamps exposure_begin_t / exposure_end_t (arrays of the "
@@ -413,6 +451,8 @@ class RealBlurClipDataset:
         self.time_bins, self.interp_num = int(time_bins), int(interp_num)
         self.crop = crop
         self.noise = None if noise is None else (float(noise[0]), float(noise[1]))
+        self.noise_mode = noise_mode
+        self.noise_table, self.hot_pixels = noise_law(noise_mode, self.noise, hot_pixels)
         self.device = torch.device(device)
         self.num_periods = self.clip.num_imgs - 1          # (the last frame only closes the last shutter period)
         self.items = sequence_items(self.num_periods, periods_per_seq, sliding_window_seq, periods_per_load, sliding_window_load)
@@ -456,14 +496,23 @@ class RealBlurClipDataset:
         win = self.window()
         blur = frames_to_planar(torch.from_numpy(frames).to(dev), window=win)                # [L,3,h,w]
         to = lambda a, dt: torch.from_numpy(a).to(dev, dt)
-        stack = torch.stack([events_to_stack(to(xs, torch.float64), to(ys, torch.float64), to(ts, torch.float64),
-                                             to(ps, torch.float32), self.time_bins, sensor_size=res).transpose(0, 1)
-                             for xs, ys, ts, ps in events])                                  # [L,TB,2,H,W]
-        if win is not None:
-            i, j, th, tw = win
-            stack = stack[..., i:i + th, j:j + tw]
-        if self.noise is not None:
-            stack = add_noise(stack, seed + 3, *self.noise)
+        stacks = [events_to_stack(to(xs, torch.float64), to(ys, torch.float64), to(ts, torch.float64), to(ps, torch.float32),
+                                  self.time_bins, sensor_size=res).transpose(0, 1) for xs, ys, ts, ps in events]
+        if self.noise_mode == "device":
+            from .eventaug import add_hot_pixels, augment_events
+            h, w = res if win is None else win[2:]
+            stack = torch.empty((len(stacks), self.time_bins, 2, h, w), dtype=torch.float32, device=dev)
+            for l, s in enumerate(stacks):          # (the noise field is one over the item: each load adds its own cells of it)
+                augment_events(s, win, False, False, seed + 3, self.noise_table, out=stack[l], cell_offset=l * stack[l].numel())
+            if self.hot_pixels is not None:
+                add_hot_pixels(stack, seed + 4, *self.hot_pixels)
+        else:
+            stack = torch.stack(stacks)                                                      # [L,TB,2,H,W]
+            if win is not None:
+                i, j, th, tw = win
+                stack = stack[..., i:i + th, j:j + tw]
+            if self.noise is not None:
+                stack = add_noise(stack, seed + 3, *self.noise)
         return {"SeqBlurryF": blur[:, None].contiguous(), "SeqHREv": stack.contiguous(), "RelativeLatentTs": rel_ts.to(dev),
                 "SeqExposureDuty": duty.to(dev)}
 
@@ -471,11 +520,14 @@ class RealBlurClipDataset:
 SUPPORTED_AUGMENT_ORDER = ["RandomCrop", "CenterCrop", "HorizontalFlip", "VertivcalFlip", "Noise", "HotPixel"]
 
 
-def dataset_args_from_config(ds_cfg):
+def dataset_args_from_config(ds_cfg, hot_pixels=False):
     """The reference's `train_dataloader.dataset` keys (config/train_ours.yml:115-150) -> ClipDataset keyword arguments.
     Everything the keys can ask for that this reader does NOT do is refused here instead of being ignored silently
-    (round-4 advisory): another `augment` order than the shipped one (crops, then flips, then noise) and scale / ori_scale pairs whose ground truth is not the 'ori' groups of a clip.  hot_pixel needs no code: the
-    reference's own test `type == [...]` (h5dataset.py:436) is never true, so it never adds hot pixels."""
+    (round-4 advisory): another `augment` order than the shipped one (crops, then flips, then noise) and scale / ori_scale pairs whose ground truth is not the 'ori' groups of a clip.  Hot pixels are opt-in: the
+    reference's own test `type == [...]` (h5dataset.py:436) is never true, so it never adds any and the default skips the
+    `hot_pixel` keys; with hot_pixels=True, 'HotPixel' in the `augment` list and `hot_pixel.enabled`, the result carries
+    `hot_pixels=(hot_pixel_std, hot_pixel_fraction)` -- the law add_hot_pixels describes, which the datasets draw on the
+    device (noise_mode="device")."""
     aug = ds_cfg.get("data_augment") or {}
     out = dict(crop=None, crop_mode="random", center_crop=None, flips=False, flip_probs=(0.5, 0.5), noise=None)
     # the tensors the model sees come from the reference's `gt_prex` groups (h5dataset.py:36-100): 'ori' exactly when `scale`
@@ -493,6 +545,9 @@ def dataset_args_from_config(ds_cfg):
     if known != [m for m in SUPPORTED_AUGMENT_ORDER if m in known] or len(known) != len(order):
         raise NotImplementedError("data_augment.augment %r: supported is the shipped order %r (crops before flips) or a "
                                   "sub-list of it" % (order, SUPPORTED_AUGMENT_ORDER))
+    hp = aug.get("hot_pixel") or {}
+    if hot_pixels and hp.get("enabled") and "HotPixel" in order:          # (defaults of add_hot_pixels, h5dataset.py:446)
+        out["hot_pixels"] = (float(hp.get("hot_pixel_std", 1.0)), float(hp.get("hot_pixel_fraction", 0.001)))
     nz = aug.get("noise") or {}
     if nz.get("enabled") and "Noise" in order:          # (h5dataset.py:432-433: defaults of add_noise where a key is absent)
         out["noise"] = (float(nz.get("noise_std", 1.0)), float(nz.get("noise_fraction", 0.1)))

@@ -75,7 +75,8 @@ from models.Ours.model_singleframe import EVFIAutoEx  # noqa: E402,F401  (resolv
 REFERENCE_DATASET_DEFAULTS = dict(scale=4, ori_scale="down4", time_bins=1, interp_num=16, NumFramePerPeriod=16, NumFramePerBlurry=9,
                                   NumPeriodPerSeq=2, SlidingWindowSeq=2, NumPeriodPerLoad=2, SlidingWindowLoad=2,
                                   ExposureMethod="Fixed", ExposureTime=None, DeblurPretrain=False,
-                                  noise=dict(enabled=True, noise_std=1.0, noise_fraction=0.05), center_crop=None)
+                                  noise=dict(enabled=True, noise_std=1.0, noise_fraction=0.05), center_crop=None,
+                                  hot_pixel=dict(enabled=True, hot_pixel_std=2.0, hot_pixel_fraction=0.001))
 
 
 def warn(msg):
@@ -139,6 +140,14 @@ def get_flags(argv=None):
                          "and --lpips_backbone torchvision's VGG-16 state dict (vgg16-397923af.pth); the yml key stays `lpips`")
     ap.add_argument("--data_seed", type=int, default=123, help="base of the per-item seeds (noise draw); the reference seeds "
                                                                 "python's generator with 123 and draws one seed per item")
+    ap.add_argument("--event-noise", dest="event_noise", default="host", choices=["host", "device"],
+                    help="with --data_list: 'host' draws the event noise as the reference does, bit for bit, on one host thread "
+                         "(about a second per 720 x 1280 load); 'device' draws a counter-based law of the same distribution in "
+                         "the kernel that cuts the event stack (ebfi_amd.eventaug)")
+    ap.add_argument("--hot-pixels", dest="hot_pixels", action="store_true",
+                    help="with --data_list and --event-noise device: honour the reference's hot_pixel section (std 2.0 on a "
+                         "fraction 0.001 of the pixels, switched with the noise by --noise_enabled; the reference's own guard "
+                         "never lets it run)")
     ap.add_argument("--batch", type=int, default=4, help="synthetic mode (no --data_list)")
     ap.add_argument("--height", type=int, default=256)
     ap.add_argument("--width", type=int, default=256)
@@ -174,6 +183,10 @@ def dataset_settings(flags):
     if flags.noise_std is not None:
         ds["noise"].update(enabled=True, noise_std=flags.noise_std, noise_fraction=0.05)
     ds["noise"]["enabled"] = bool(flags.noise_enabled)           # (:329-331: the flag decides last)
+    ds["event_noise"] = getattr(flags, "event_noise", "host")    # (this implementation's own: the law, and the hot pixels)
+    ds["hot_pixel"]["enabled"] = bool(flags.noise_enabled)       # (:345: switched together with the noise)
+    ds["hot_pixels"] = ((ds["hot_pixel"]["hot_pixel_std"], ds["hot_pixel"]["hot_pixel_fraction"])
+                        if getattr(flags, "hot_pixels", False) and ds["hot_pixel"]["enabled"] else None)
     if flags.center_crop_size is not None:
         ds["center_crop"] = list(flags.center_crop_size) * (2 if len(flags.center_crop_size) == 1 else 1)
     notes = []
@@ -264,7 +277,7 @@ def infer_clip(interp, data_path, ds_cfg, root_path, device, seed, png=False, me
     data = clipdata.ClipDataset(data_path, time_bins=int(ds_cfg["time_bins"]), frames_per_period=int(ds_cfg["NumFramePerPeriod"]),
                                 frames_per_blurry=int(ds_cfg["NumFramePerBlurry"]), exposure_method=ds_cfg["ExposureMethod"],
                                 exposure_time=ds_cfg["ExposureTime"], crop=ds_cfg["center_crop"], crop_mode="center", flips=False,
-                                device=device, seed=seed,
+                                device=device, seed=seed, noise_mode=ds_cfg.get("event_noise", "host"), hot_pixels=ds_cfg.get("hot_pixels"),
                                 noise=(ds_cfg["noise"]["noise_std"], ds_cfg["noise"]["noise_fraction"]) if ds_cfg["noise"]["enabled"] else None)
     seqs = clipdata.sequence_items(len(data), ds_cfg["NumPeriodPerSeq"], ds_cfg["SlidingWindowSeq"], ds_cfg["NumPeriodPerLoad"],
                                    ds_cfg["SlidingWindowLoad"])
@@ -373,7 +386,8 @@ def infer_clip_real(interp, data_path, ds_cfg, root_path, device, seed, png=Fals
     data = clipdata.RealBlurClipDataset(data_path, time_bins=int(ds_cfg["time_bins"]), interp_num=int(ds_cfg["interp_num"]),
                                         periods_per_seq=ds_cfg["NumPeriodPerSeq"], sliding_window_seq=ds_cfg["SlidingWindowSeq"],
                                         periods_per_load=ds_cfg["NumPeriodPerLoad"], sliding_window_load=ds_cfg["SlidingWindowLoad"],
-                                        crop=ds_cfg["center_crop"], device=device,
+                                        crop=ds_cfg["center_crop"], device=device, noise_mode=ds_cfg.get("event_noise", "host"),
+                                        hot_pixels=ds_cfg.get("hot_pixels"),
                                         noise=(ds_cfg["noise"]["noise_std"], ds_cfg["noise"]["noise_fraction"]) if ds_cfg["noise"]["enabled"] else None)
     img_path = os.path.join(root_path, "img")
     os.makedirs(root_path, exist_ok=False)                # (like the reference: an existing result is never overwritten)
@@ -423,6 +437,15 @@ def infer_clip_real(interp, data_path, ds_cfg, root_path, device, seed, png=Fals
     return iF + 1, spent
 
 
+def noise_law_name(ds_cfg):
+    """The active event-noise law, for the summary line."""
+    hot = ", hot pixels std %g fraction %g" % tuple(ds_cfg["hot_pixels"]) if ds_cfg.get("hot_pixels") else ""
+    if not ds_cfg["noise"]["enabled"]:
+        return "off" + hot
+    return "%s law, std %g on a fraction %g of the cells%s" % (ds_cfg.get("event_noise", "host"), ds_cfg["noise"]["noise_std"],
+                                                             ds_cfg["noise"]["noise_fraction"], hot)
+
+
 def run_data_list(flags, interp, device):
     ds_cfg, notes = dataset_settings(flags)
     for n in notes:
@@ -465,7 +488,8 @@ def run_data_list(flags, interp, device):
         frames, spent = frames + n, spent + s
         if r is not None:
             results.append((os.path.basename(data_path),) + r)
-    print("restored %d frames of %d clip(s) in %.3f s inside the model: %.1f frames/s" % (frames, len(paths), spent, frames / max(spent, 1e-9)))
+    print("restored %d frames of %d clip(s) in %.3f s inside the model: %.1f frames/s; event noise: %s"
+          % (frames, len(paths), spent, frames / max(spent, 1e-9), noise_law_name(ds_cfg)))
     if metrics:
         # (written once every clip is done: a run refused half-way leaves an earlier run's summaries as they were)
         all_, all_step = summarise_clips(results, "inference %s \n on %s" % ([flags.model_path], paths))

@@ -242,7 +242,8 @@ def resume_checkpoint(path, eng, scheduler, config, reset=False, map_location="c
 
 
 def add_loader_arguments(ap):
-    """--loader / --prefetch of the recorded-clip readers (train_ours.py and train_ours_exposuredecision.py)."""
+    """--loader / --prefetch / --event-noise / --hot-pixels of the recorded-clip readers (train_ours.py and
+    train_ours_exposuredecision.py); they apply to the training and the validation set alike."""
     ap.add_argument("--loader", default="device", choices=["device", "host"],
                     help="recorded clips: 'device' uploads the crop window's rows as uint8 and makes the sharp planes and the "
                          "blurry mean in one kernel; 'host' converts and averages whole frames on the host.  The tensors are "
@@ -250,6 +251,13 @@ def add_loader_arguments(ap):
     ap.add_argument("--prefetch", type=int, default=1,
                     help="recorded clips: batches whose host half (file reads, staging, noise draw) a worker thread prepares "
                          "ahead while the current batch trains; 0 = everything synchronously in the training loop")
+    ap.add_argument("--event-noise", dest="event_noise", default="host", choices=["host", "device"],
+                    help="recorded clips, data_augment.noise: 'host' draws the event noise as the reference does, bit for bit, on "
+                         "one host thread; 'device' draws a counter-based law of the same distribution in the kernel that cuts "
+                         "and flips the event stack (ebfi_amd.eventaug) -- other bits, no host work")
+    ap.add_argument("--hot-pixels", dest="hot_pixels", action="store_true",
+                    help="recorded clips: honour data_augment.hot_pixel (the reference's own guard never lets it run); needs "
+                         "--event-noise device")
 
 
 def add_monitor_arguments(ap):
@@ -276,24 +284,34 @@ def build_monitor(config, args, runid, rank, eng, default_experiment="Ours"):
 DEFAULT_EXPOSURE_TIME = [9, 10, 11, 12, 13, 14, 15]      # ExposureTime of the reference's train_ours.yml (Custom exposure)
 
 
+def with_noise_law(ds_cfg, event_noise="host", hot_pixels=False):
+    """A copy of a dataset section carrying the flags --event-noise / --hot-pixels as the keys `event_noise` and `hot_pixels`
+    that `clip_dataset` reads (the flags decide; a section may also name them itself)."""
+    return dict(ds_cfg, event_noise=event_noise, hot_pixels=bool(hot_pixels))
+
+
 def clip_dataset(path, ds_cfg, time_bins, default_exposure_time, device, seed, loader):
     """The recorded-clip dataset of both trainers, for training and validation alike: `ds_cfg` is a dataset section of the config
     with the reference's keys (train_ours.yml:115-150); absent keys take its shipped values, `time_bins` and
-    `default_exposure_time` being the calling script's."""
+    `default_exposure_time` being the calling script's.  Two keys are this project's: `event_noise` ('host', the default, or
+    'device') names the noise law and `hot_pixels` (default false) honours data_augment.hot_pixel (`with_noise_law`)."""
     from ebfi_amd import clipdata
     return clipdata.ClipDataset(path, time_bins=int(ds_cfg.get("time_bins", time_bins)),
                                 frames_per_period=int(ds_cfg.get("NumFramePerPeriod", 16)),
                                 frames_per_blurry=int(ds_cfg.get("NumFramePerBlurry", 16)),
                                 exposure_method=ds_cfg.get("ExposureMethod", "Custom"),
                                 exposure_time=ds_cfg.get("ExposureTime", default_exposure_time),
-                                device=device, seed=seed, frames=loader, **clipdata.dataset_args_from_config(ds_cfg))
+                                device=device, seed=seed, frames=loader, noise_mode=ds_cfg.get("event_noise", "host"),
+                                **clipdata.dataset_args_from_config(ds_cfg, hot_pixels=bool(ds_cfg.get("hot_pixels", False))))
 
 
-def real_data_passes(path, config, B, TB, device, rank, world, seed, loader="device", prefetch=1):
+def real_data_passes(path, config, B, TB, device, rank, world, seed, loader="device", prefetch=1, event_noise="host",
+                     hot_pixels=False):
     """Endless stream of (Frame, Event, T, GTEx, LatentF) passes from recorded clips (ebfi_amd.clipdata): the dataset keys
     are the reference's (config train_dataloader.dataset, train_ours.yml:115-150); defaults = its shipped values."""
     from ebfi_amd import clipdata
-    ds = clip_dataset(path, (config.get("train_dataloader") or {}).get("dataset") or {}, TB, DEFAULT_EXPOSURE_TIME, device, seed, loader)
+    ds_cfg = with_noise_law((config.get("train_dataloader") or {}).get("dataset") or {}, event_noise, hot_pixels)
+    ds = clip_dataset(path, ds_cfg, TB, DEFAULT_EXPOSURE_TIME, device, seed, loader)
     if len(ds) < B * world:
         raise SystemExit("--data: %d periods in %s, need at least batch_size x world = %d" % (len(ds), path, B * world))
     for batch in clipdata.batches(ds, B, rank=rank, world=world, seed=seed, prefetch=prefetch):
@@ -307,7 +325,7 @@ def validation_batches(vs, config, args, B, H, W, TB, device, rank, world):
     (reference keys); without a path: `valid_batches` synthetic periods, made once and kept on the device."""
     from ebfi_amd import clipdata
     from ebfi_amd.engine import synthetic_validation_batch
-    ds_cfg = vs["dataset"]
+    ds_cfg = with_noise_law(vs["dataset"], args.event_noise, args.hot_pixels)
     vb = vs["batch_size"] or B
     if vs["valid_data"]:
         ds = clip_dataset(vs["valid_data"], ds_cfg, TB, DEFAULT_EXPOSURE_TIME, device, args.seed, args.loader)
@@ -486,7 +504,8 @@ def main(argv=None):
     out_dir = os.path.join(tr.get("output_path", "./output"), "models", config.get("experiment", "Ours"), args.runid)
 
     make = synthetic_batch_from_raw_events if args.raw_events else synthetic_batch
-    real = real_data_passes(args.data, config, B, TB, device, rank, world, args.seed, args.loader, args.prefetch) if args.data else None
+    real = real_data_passes(args.data, config, B, TB, device, rank, world, args.seed, args.loader, args.prefetch, args.event_noise,
+                            args.hot_pixels) if args.data else None
     valid_batches, tracker = None, None
     if vs["do_validation"]:
         from ebfi_amd.metrics import MetricTracker

@@ -30,7 +30,7 @@ sys.path.insert(0, HERE)
 
 from train_ours import (CHECKPOINT_KEYS, TRAINING_MODE, Monitor, add_loader_arguments, add_monitor_arguments,  # noqa: E402,F401
                         best_checkpoint_name, build_lr_scheduler, build_monitor, checkpoint_state, clip_dataset, init_distributed_mode,
-                        optimizer_settings, resume_checkpoint, save_checkpoint, train_loop, trainer_settings, validation_seeds, validation_settings)
+                        optimizer_settings, resume_checkpoint, save_checkpoint, train_loop, trainer_settings, validation_seeds, validation_settings, with_noise_law)
 from ebfi_amd.exposure_engine import (BLURRY_FASHIONS, check_fashion, check_model_name,  # noqa: E402,F401
                                       synthetic_exposure_batch)
 
@@ -87,12 +87,13 @@ def exposure_settings(config):
             "height": int(tr.get("height", 128)), "width": int(tr.get("width", 128))}
 
 
-def real_data_periods(path, config, es, device, rank, world, seed, loader="device", prefetch=1):
+def real_data_periods(path, config, es, device, rank, world, seed, loader="device", prefetch=1, event_noise="host",
+                      hot_pixels=False):
     """Endless stream of (Frame [B,3,H,W], Event [B,TB,2,H,W], Duty [B,1]) micro-steps from recorded clips: one per period of
     every load of a collated batch, in the reference's order (:221-231)."""
     from ebfi_amd import clipdata
-    ds = clip_dataset(path, (config.get("train_dataloader") or {}).get("dataset") or {}, es["TB"], DEFAULT_EXPOSURE_TIME, device, seed,
-                      loader)
+    ds_cfg = with_noise_law((config.get("train_dataloader") or {}).get("dataset") or {}, event_noise, hot_pixels)
+    ds = clip_dataset(path, ds_cfg, es["TB"], DEFAULT_EXPOSURE_TIME, device, seed, loader)
     B = es["batch_size"]
     if len(ds) < B * world:
         raise SystemExit("--data: %d periods in %s, need at least batch_size x world = %d" % (len(ds), path, B * world))
@@ -109,7 +110,8 @@ def validation_batches(vs, es, args, device, rank, world):
     from ebfi_amd import clipdata
     vb = vs["batch_size"] or es["batch_size"]
     if vs["valid_data"]:
-        ds = clip_dataset(vs["valid_data"], vs["dataset"], es["TB"], DEFAULT_EXPOSURE_TIME, device, args.seed, args.loader)
+        ds_cfg = with_noise_law(vs["dataset"], args.event_noise, args.hot_pixels)
+        ds = clip_dataset(vs["valid_data"], ds_cfg, es["TB"], DEFAULT_EXPOSURE_TIME, device, args.seed, args.loader)
         if len(ds) == 0:
             raise SystemExit("--valid-data: no complete period in %s" % vs["valid_data"])
         return lambda: clipdata.eval_batches(ds, vb, rank=rank, world=world, seed=args.seed, drop_last=vs["drop_last"],
@@ -148,7 +150,8 @@ def main(argv=None):
     runid = args.runid or str(config.get("id") or "run")
     out_dir = os.path.join(tr.get("output_path", "./output"), "models", config.get("experiment", "ExposurePretrain"), runid)
 
-    real = real_data_periods(args.data, config, es, device, rank, world, args.seed, args.loader, args.prefetch) if args.data else None
+    real = real_data_periods(args.data, config, es, device, rank, world, args.seed, args.loader, args.prefetch, args.event_noise,
+                             args.hot_pixels) if args.data else None
     valid_batches, tracker = None, None
     if vs["do_validation"]:
         valid_batches = validation_batches(vs, es, args, device, rank, world)

@@ -40,6 +40,9 @@
  *   ebfi_frames_u8_to_planar    GetFrames of the real-data reader (dataloader/h5dataset_realdata.py:178-189) + AugmentData's crop / flips
  *   ebfi_planar_to_u8           the uint8 image cast of the evaluation loop (infer_ours.py:135)
  *   ebfi_period_frames_u8       GetFrames of the synthetic-blur reader (dataloader/h5dataset.py:296-311): sharp frames + exposure mean
+ *   ebfi_event_augment / ebfi_event_hot_pixels
+ *                               AugmentData's crop, flips, add_noise and add_hot_pixels on the event stack
+ *                               (dataloader/h5dataset.py:368-463), with a counter-based integer noise law
  *   ebfi_event_cnt_image        event_visualisation.plot_event_cnt of the evaluation loop (infer_ours.py:139-142,
  *                               myutils/vis_events/matplotlib_plot_events.py:127-251)
  *   ebfi_segment_stats          per-layer weight / gradient moments and histograms of the training monitor (no counterpart in the
@@ -105,7 +108,8 @@ extern "C" {
  *      likewise; and ebfi_optim_step (Adam / AdamW with weight decay and AMSGrad, SGD with momentum: the optimiser section of
  *      the training config), likewise; and ebfi_conv2d_backward_weight_f16g_multi_workspace /
  *      ebfi_conv2d_backward_weight_f16g_multi (the pure weight gradients of a training step, deferred and run in one launch) and
- *      ebfi_gather_sum_multi (their fold gathers), likewise */
+ *      ebfi_gather_sum_multi (their fold gathers), likewise; and ebfi_event_augment / ebfi_event_hot_pixels (the device noise
+ *      law of the clip loaders), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -904,6 +908,39 @@ int ebfi_planar_to_u8(const float *in, const int64_t in_strides[3], int64_t n, i
 int ebfi_period_frames_u8(const uint8_t *src, const int64_t src_strides[3], int64_t n, int64_t n_blur, int H0, int W0, int i,
                           int j, int h, int w, int reverse_channels, int flip_h, int flip_v, float *sharp, float *blur,
                           void *stream);
+
+/* ------------------------------------------------------------------ event augmentation of the clip loaders, device law
+ * The device-native counterpart of AugmentData's crop / flips / add_noise / add_hot_pixels on an event stack
+ * (dataloader/h5dataset.py:368-463).  The random law is integer-only, so a host restatement gives the same bits:
+ *   generator  Philox4x32-10, key = (seed low word, seed high word), counter = (g low, g high, stream, 0), four words per call;
+ *   count      a draw of one word u gives k = #{m : u < table[m]}, table[m] = floor(2^32 f erfc((m + 1) / (std sqrt 2))) made
+ *              on the HOST, strictly decreasing, at most EBFI_NOISE_TABLE_MAX entries: the distribution of int(|N(0, std)|)
+ *              on a fraction f of the draws.  No transcendental runs on the device.
+ *
+ * ebfi_event_augment: source float32 [TB][2][H0][W0] (value (b, p, Y, X) at src + b * src_strides[0] + p * src_strides[1] +
+ * Y * src_strides[2] + X: a transposed view is read in place) -> dst float32 [TB][2][h][w], contiguous:
+ *   dst[b][p][y][x] = src[b][p][i + (flip_v ? h-1-y : y)][j + (flip_h ? w-1-x : x)] + k(cell)
+ * where cell = cell_offset + the linear index in dst and k(cell) is the count drawn from word (cell & 3) of Philox group
+ * (cell >> 2) of stream 0.  cell_offset is 0 for an item made in one call; an item of several loads passes each load's first
+ * cell.  table_len == 0: no noise (k = 0), `table` may then be null.  A thread owns four consecutive cells of dst: one
+ * 16-byte store when dst is 16-byte aligned; one 16-byte load when its four cells lie in one row and their source address is
+ * 16-byte aligned (mirrored in registers under flip_h), scalar loads otherwise; the last cells of a stack whose size is no
+ * multiple of 4 are stored one by one.  Cell indices are 64-bit.  One launch on `stream`, no workspace, no synchronisation.
+ * Null pointers, TB < 1, sizes < 1, a window that leaves the frame, h * w >= 2^31, a negative stride, a negative cell_offset,
+ * table_len outside [0, EBFI_NOISE_TABLE_MAX], source and destination ranges that overlap -> EBFI_ERR_ARG, nothing launched.
+ *
+ * ebfi_event_hot_pixels: in place on stack float32 [planes][h][w], contiguous.  Hot pixel n < n_hot takes words u0, u1, u2 of
+ * group n of stream 1: x = (u0 * w) >> 32, y = (u1 * h) >> 32, amplitude k from u2 through `table` (made with f = 1); k is
+ * added to every plane at (y, x), repeated positions accumulate.  The adds are float atomics of integers: exact and
+ * order-free while every sum stays below 2^24, so the result does not depend on the launch geometry.  n_hot == 0 or
+ * table_len == 0 is a no-op.  Null stack, sizes < 1, h * w >= 2^31, n_hot < 0 or planes * n_hot >= 2^40, table_len outside
+ * [0, EBFI_NOISE_TABLE_MAX] -> EBFI_ERR_ARG. */
+#define EBFI_NOISE_TABLE_MAX 32
+int ebfi_event_augment(const float *src, const int64_t src_strides[3], int64_t TB, int H0, int W0, int i, int j, int h, int w,
+                       int flip_h, int flip_v, uint64_t seed, const uint32_t *table, int table_len, int64_t cell_offset,
+                       float *dst, void *stream);
+int ebfi_event_hot_pixels(float *stack, int64_t planes, int h, int w, uint64_t seed, const uint32_t *table, int table_len,
+                          int64_t n_hot, void *stream);
 
 /* ------------------------------------------------------------------ event-count images of the evaluation loop
  * ebfi_event_cnt_image: n images of two polarity planes, float32 (value (f, p, y, x) at ev + f * ev_strides[0] + p * ev_strides[1]
