@@ -1,6 +1,10 @@
 """ctypes binding of libebfi_hip.so (the C ABI declared in include/ebfi_hip.h).
 
-This is the only place the host code touches the native library.  Loading is lazy and LOUD: if the
+This is the only place the host code touches the native library.  The header is the single description
+of the ABI: at import ``parse_header`` reads it (text only, no library) into ``SIGNATURES``
+{name: (restype, [argtypes])}, ``PARAMS`` {name: [parameter declarations]} and ``CONSTANTS`` (enumerators
+and ``#define EBFI_*`` integers), and refuses whatever its type rules do not cover.  A new entry point is
+declared in the header and defined in csrc/; nothing is written here.  Loading is lazy and LOUD: if the
 shared object is missing, cannot be loaded or lacks a declared symbol, the first use of any op
 raises ``EbfiNativeError`` -- there is no CPU or PyTorch fallback anywhere in this package.
 """
@@ -30,10 +34,6 @@ LIB_PATH = dev_env("EBFI_LIB_PATH") or os.path.join(PKG_ROOT, "lib", "libebfi_hi
 HEADER = os.path.join(REPO_ROOT, "include", "ebfi_hip.h")
 BUILD_SCRIPT = os.path.join(PKG_ROOT, "csrc", "build.sh")
 
-EBFI_F32, EBFI_F32_BF16MMA, EBFI_F32_BF16X3MMA = 0, 2, 3
-EBFI_ERR_UNSUPPORTED = -3   # include/ebfi_hip.h ebfi_status
-ABI_VERSION = 14         # include/ebfi_hip.h EBFI_ABI_VERSION
-
 
 class EbfiNativeError(RuntimeError):
     pass
@@ -43,156 +43,77 @@ _lock = threading.Lock()
 _lib = None
 
 _c = ctypes
-_vp, _i, _i64, _sz = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_size_t
-_p64 = _c.POINTER(_c.c_int64)
+_vp, _i, _i64 = _c.c_void_p, _c.c_int, _c.c_int64
+_SCALARS = {"int": _i, "int64_t": _i64, "size_t": _c.c_size_t, "float": _c.c_float, "double": _c.c_double,
+            "uint64_t": _c.c_uint64}
+_RETURNS = dict(_SCALARS, **{"void": None, "const char *": _c.c_char_p})
+_INT = r"-?(?:0[xX][0-9a-fA-F]+|\d+)"
 
-# name -> (restype, argtypes); must list every function the header declares (tests check that)
-SIGNATURES = {
-    "ebfi_abi_version": (_i, []),
-    "ebfi_last_error": (_c.c_char_p, []),
-    "ebfi_fac_forward": (_i, [_vp, _p64, _p64, _vp, _p64, _p64, _i, _vp, _p64, _p64, _i, _vp]),
-    "ebfi_fac_backward": (_i, [_vp, _p64, _p64, _vp, _p64, _p64, _i, _vp, _p64, _vp, _p64, _vp, _p64, _i, _vp]),
-    "ebfi_fac_backward_ex": (_i, [_vp, _p64, _p64, _vp, _p64, _p64, _i, _vp, _p64, _vp, _p64, _vp, _p64, _c.c_float, _i, _vp]),
-    "ebfi_dcn_forward": (_i, [_vp] * 6 + [_i] * 14 + [_i, _vp]),
-    "ebfi_dcn_backward_workspace": (_sz, [_i] * 14 + [_i]),
-    "ebfi_dcn_backward": (_i, [_vp] * 11 + [_i] * 14 + [_vp, _sz, _i, _vp]),
-    "ebfi_conv2d_forward": (_i, [_vp] * 4 + [_i] * 8 + [_i, _c.c_float, _i, _vp]),
-    "ebfi_conv2d_backward_data": (_i, [_vp] * 4 + [_i] * 8 + [_i, _c.c_float, _i, _vp]),
-    "ebfi_conv2d_backward_weight_workspace": (_sz, [_i] * 8 + [_i]),
-    "ebfi_conv2d_backward_weight": (_i, [_vp] * 5 + [_i] * 8 + [_i, _c.c_float, _vp, _sz, _i, _vp]),
-    "ebfi_conv2d_backward_weight_ex": (_i, [_vp] * 6 + [_i] * 8 + [_i, _c.c_float, _vp, _sz, _i, _vp]),
-    "ebfi_conv2d_bf16_workspace": (_sz, [_i, _i, _i]),
-    "ebfi_conv2d_forward_bf16mma": (_i, [_vp] * 4 + [_i] * 8 + [_i, _c.c_float, _vp, _sz, _vp]),
-    "ebfi_conv2d_backward_data_bf16mma": (_i, [_vp] * 4 + [_i] * 8 + [_i, _c.c_float, _vp, _sz, _vp]),
-    "ebfi_conv2d_forward_bf16x3": (_i, [_vp] * 4 + [_i] * 8 + [_i, _c.c_float, _vp, _sz, _vp]),
-    "ebfi_conv2d_backward_data_bf16x3": (_i, [_vp] * 4 + [_i] * 8 + [_i, _c.c_float, _vp, _sz, _vp]),
-    "ebfi_conv2d_packed_bytes": (_sz, [_i, _i, _i, _i]),
-    "ebfi_conv2d_pack_bf16x3": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "ebfi_pack_table_bf16": (_i, [_vp, _vp, _i64, _vp, _vp]),
-    "ebfi_pack_pairs_block": (_i, []),
-    "ebfi_pack_pairs_bf16": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
-    "ebfi_f16_scales_finish": (_i, [_vp, _i, _vp, _vp]),
-    "ebfi_pack_table_f16": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "ebfi_conv2d_packed_f16": (_i, [_vp, _vp, _sz, _vp, _vp] + [_i] * 8 + [_i, _c.c_float, _vp, _vp, _i, _c.c_float, _vp, _vp, _vp]),
-    "ebfi_conv2d_backward_weight_f16g": (_i, [_vp] * 6 + [_i] * 8 + [_i, _c.c_float, _vp, _vp, _vp, _sz, _vp]),
-    "ebfi_conv2d_backward_weight_f16g_ex": (_i, [_vp] * 6 + [_i] * 9 + [_i, _c.c_float, _vp, _vp, _vp, _sz, _vp]),
-    "ebfi_to_c16": (_i, [_vp, _vp, _c.c_float, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ebfi_to_c16_cat2": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
-    "ebfi_conv2d_packed_x3_c16": (_i, [_vp, _vp, _sz, _vp, _vp] + [_i] * 8 + [_i, _c.c_float, _vp, _vp, _i, _c.c_float, _vp, _vp, _i, _vp]),
-    "ebfi_conv2d_packed_f16_c16": (_i, [_vp, _i, _vp, _sz, _vp, _vp] + [_i] * 8 + [_i, _c.c_float, _vp, _vp, _i, _c.c_float,
-                                        _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "ebfi_conv2d_backward_weight_f16c": (_i, [_vp, _vp, _i, _vp, _vp] + [_i] * 6 + [_vp, _vp, _vp, _sz, _vp]),
-    "ebfi_conv2d_backward_weight_f16c_batch_workspace": (_sz, [_i, _vp, _vp]),
-    "ebfi_conv2d_backward_weight_f16c_batch": (_i, [_i] + [_vp] * 9 + [_i, _i, _i, _vp, _sz, _vp]),
-    "ebfi_conv2d_backward_weight_f16g_multi_workspace": (_sz, [_i] + [_vp] * 5),
-    "ebfi_conv2d_backward_weight_f16g_multi": (_i, [_i] + [_vp] * 15 + [_vp, _sz, _vp]),
-    "ebfi_fac_forward_p16": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ebfi_fac_backward_p16": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_float, _i, _i, _i, _i, _i, _vp]),
-    "ebfi_scale_residual_cat_forward_c16": (_i, [_vp] * 8 + [_i, _i, _i, _i, _i64, _vp]),
-    "ebfi_scale_residual_cat_backward_slices": (_i, []),
-    "ebfi_scale_residual_cat_backward_c16": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i64, _c.c_float, _vp]),
-    "ebfi_scale_residual_cat_backward_c16a": (_i, [_vp] * 10 + [_i, _i, _i, _i, _c.c_float, _vp]),
-    "ebfi_conv2d_packed_x3_rc": (_i, [_vp, _vp, _sz, _vp, _vp] + [_i] * 6 + [_c.c_float, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    "ebfi_conv2d_thin_forward": (_i, [_vp, _vp, _vp, _vp] + [_i] * 8 + [_i, _c.c_float, _vp]),
-    "ebfi_kernelconv_fac_fused_x3": (_i, [_vp, _vp, _sz, _vp, _vp, _vp] + [_i] * 6 + [_c.c_float, _vp]),
-    "ebfi_kernelconv_fac_fused_f16": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp] + [_i] * 6 + [_c.c_float, _vp, _vp, _vp]),
-    "ebfi_conv2d_packed_x3": (_i, [_vp, _vp, _sz, _vp, _vp] + [_i] * 8 + [_i, _c.c_float, _vp, _vp, _i, _c.c_float, _vp]),
-    "ebfi_conv2d_backward_weight_x3g": (_i, [_vp] * 4 + [_i] * 8 + [_vp, _sz, _vp]),
-    "ebfi_scale_residual_cat_forward_ex": (_i, [_vp] * 6 + [_i, _i, _i64, _i64, _vp]),
-    "ebfi_scale_residual_cat_backward_ex": (_i, [_vp] * 10 + [_i, _i, _i64, _i64, _i64, _i, _c.c_float, _vp]),
-    "ebfi_scalar_conv_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _c.c_float, _vp]),
-    "ebfi_scalar_conv_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _c.c_float, _vp]),
-    "ebfi_events_workspace": (_sz, [_i]),
-    "ebfi_events_to_stack": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "ebfi_frame2lap": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "ebfi_frame2dcp": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ebfi_scale_residual_cat_forward": (_i, [_vp] * 6 + [_i, _i, _i64, _vp]),
-    "ebfi_scale_residual_cat_backward": (_i, [_vp] * 10 + [_i, _i, _i64, _vp]),
-    "ebfi_prodmean_forward": (_i, [_vp, _vp, _vp, _i64, _i64, _vp]),
-    "ebfi_prodmean_backward": (_i, [_vp] * 5 + [_i64, _i64, _vp]),
-    "ebfi_gather_sum": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
-    "ebfi_gather_sum_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ebfi_se_gate_workspace": (_c.c_size_t, [_i, _i, _i64]),
-    "ebfi_se_gate_forward": (_i, [_vp] * 8 + [_i, _i, _i64, _i, _c.c_float, _vp]),
-    "ebfi_se_gate_backward": (_i, [_vp] * 11 + [_i, _i, _i64, _i, _c.c_float, _vp]),
-    "ebfi_conv2d_packed_x3_shuffled": (_i, [_vp, _vp, _c.c_size_t, _vp, _vp] + [_i] * 6 + [_c.c_float, _i, _vp]),
-    "ebfi_conv2d_packed_f16_shuffled": (_i, [_vp, _i, _vp, _c.c_size_t, _vp, _vp] + [_i] * 6 + [_c.c_float, _vp, _i, _c.c_float, _vp, _vp, _i, _vp]),
-    "ebfi_se_gate_forward_ps": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _c.c_float, _vp]),
-    "ebfi_se_gate_backward_ps": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _c.c_float, _vp]),
-    "ebfi_groupnorm_workspace": (_sz, [_i, _i]),
-    "ebfi_groupnorm_forward": (_i, [_vp] * 6 + [_i, _i, _i64, _i, _c.c_float, _vp, _sz, _vp]),
-    "ebfi_groupnorm_backward": (_i, [_vp] * 8 + [_i, _i, _i64, _i, _vp, _sz, _vp]),
-    "ebfi_census_partials": (_i64, [_i, _i, _i]),
-    "ebfi_census_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ebfi_census_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ebfi_census_pair_forward": (_i, [_vp, _vp, _vp, _c.c_float, _c.c_float, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ebfi_census_pair_backward": (_i, [_vp, _vp, _vp, _c.c_float, _c.c_float, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ebfi_gauss5_forward": (_i, [_vp, _vp, _i64, _i, _i, _c.c_float, _vp]),
-    "ebfi_gauss5_backward": (_i, [_vp, _vp, _i64, _i, _i, _c.c_float, _vp]),
-    "ebfi_ed_head_workspace": (_sz, [_i, _i, _i64]),
-    "ebfi_ed_head_forward": (_i, [_vp] * 7 + [_i, _i, _i64, _i, _c.c_float, _vp, _sz, _vp]),
-    "ebfi_ed_head_backward": (_i, [_vp] * 11 + [_i, _i, _i64, _i, _vp, _sz, _vp]),
-    "ebfi_conv2d_backward_data_s2_bf16x3": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "ebfi_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64] + [_c.c_double] * 4 + [_vp]),
-    "ebfi_adam_step_guarded": (_i, [_vp, _vp, _vp, _vp, _vp, _i64] + [_c.c_double] * 4 + [_vp, _vp, _vp]),
-    "ebfi_optim_step": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64] + [_c.c_double] * 7 + [_vp, _vp, _vp]),
-    "ebfi_pad2d_backward": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
-    "ebfi_grad_gather": (_i, [_vp, _vp, _i, _vp, _i64, _i, _vp, _vp]),
-    "ebfi_laploss_workspace_floats": (_i64, [_i64, _i, _i, _i]),
-    "ebfi_laploss_partials": (_i64, [_i64, _i, _i, _i]),
-    "ebfi_laploss_forward": (_i, [_vp, _vp, _vp, _c.c_float, _c.c_float, _vp, _vp, _i64, _i, _i, _i, _vp]),
-    "ebfi_laploss_backward": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
-    "ebfi_image_metrics_workspace": (_i64, [_i64, _i, _i, _i]),
-    "ebfi_image_metrics": (_i, [_vp, _p64, _vp, _p64, _i64, _i, _i, _i, _c.c_float, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "ebfi_lpips_params_bytes": (_i64, []),
-    "ebfi_lpips_pack_params": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
-    "ebfi_lpips_workspace": (_i64, [_i64, _i, _i, _i]),
-    "ebfi_lpips_alex": (_i, [_vp, _p64, _vp, _p64, _i64, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "ebfi_lpips_vgg_params_bytes": (_i64, []),
-    "ebfi_lpips_vgg_pack_params": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
-    "ebfi_lpips_vgg_workspace": (_i64, [_i64, _i, _i, _i]),
-    "ebfi_lpips_vgg": (_i, [_vp, _p64, _vp, _p64, _i64, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "ebfi_lpips_vgg_train_workspace": (_i64, [_i64, _i, _i, _i]),
-    "ebfi_lpips_vgg_forward_train": (_i, [_vp, _p64, _vp, _p64, _i64, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "ebfi_lpips_vgg_backward": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _p64, _vp]),
-    "ebfi_charbonnier_workspace": (_i64, [_i64, _i, _i, _i]),
-    "ebfi_charbonnier_forward": (_i, [_vp, _p64, _vp, _p64, _i64, _i, _i, _i, _c.c_float, _vp, _i64, _vp, _vp]),
-    "ebfi_charbonnier_backward": (_i, [_vp, _p64, _vp, _p64, _i64, _i, _i, _i, _c.c_float, _vp, _vp, _vp]),
-    "ebfi_duty_head_workspace": (_i64, [_i64, _i, _i]),
-    "ebfi_duty_head_forward": (_i, [_vp, _p64, _vp, _i64, _i, _i, _c.c_float, _vp, _i64, _vp, _vp, _vp]),
-    "ebfi_duty_head_backward": (_i, [_vp, _vp, _vp, _i64, _i, _i, _c.c_float, _vp, _vp]),
-    "ebfi_frames_u8_to_planar": (_i, [_vp, _p64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ebfi_planar_to_u8": (_i, [_vp, _p64, _i64, _i, _i, _vp, _vp]),
-    "ebfi_period_frames_u8": (_i, [_vp, _p64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "ebfi_event_augment": (_i, [_vp, _p64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _c.c_uint64, _vp, _i, _i64, _vp, _vp]),
-    "ebfi_event_hot_pixels": (_i, [_vp, _i64, _i, _i, _c.c_uint64, _vp, _i, _i64, _vp]),
-    "ebfi_event_cnt_image_workspace": (_i64, [_i64, _i, _i, _i]),
-    "ebfi_event_cnt_image": (_i, [_vp, _p64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
-    "ebfi_segment_stats_workspace": (_i64, [_i64, _i]),
-    "ebfi_segment_stats": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ebfi_esim_loop_bound": (_i64, [_vp, _c.c_double, _c.c_double]),
-    "ebfi_esim_init": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
-    "ebfi_esim_count": (_i, [_vp, _p64, _i, _i64, _i, _i, _vp, _vp, _c.c_double, _c.c_double, _c.c_double, _vp, _vp, _vp]),
-    "ebfi_esim_emit": (_i, [_vp, _p64, _i, _i64, _i, _i, _vp, _vp, _c.c_double, _c.c_double, _c.c_double, _vp, _vp, _i64,
-                            _vp, _vp, _vp, _vp, _vp]),
-    "ebfi_avgpool2_forward": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "ebfi_bilinear_up2_forward": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "ebfi_flow_max_magnitude": (_i, [_vp, _i, _i, _vp, _vp]),
-    "ebfi_slomo_assemble": (_i, [_vp, _vp, _vp, _c.c_double, _vp, _i, _i, _vp]),
-    "ebfi_slomo_blend": (_i, [_vp, _vp, _c.c_double, _vp, _vp, _i, _i, _vp]),
-    "ebfi_slomo_frame_u8": (_i, [_vp, _vp, _i, _i, _vp]),
-    "ebfi_prof_enable": (None, [_i]),
-    "ebfi_prof_set_capacity": (_i, [_i]),
-    "ebfi_prof_reset": (None, []),
-    "ebfi_prof_collect": (_i, [_c.POINTER(_i)]),
-    "ebfi_prof_num_kernels": (_i, []),
-    "ebfi_prof_get": (_i, [_i, _c.POINTER(_c.c_char_p), _c.POINTER(_i64), _c.POINTER(_c.c_double)]),
-    "ebfi_prof_get_work": (_i, [_i, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
-}
+
+def _argtype(func, decl):
+    """ctypes type of one parameter declaration.  Pointers of any depth travel as c_void_p (the ebfi_prof_*
+    out-parameters too: byref() converts to it), `const int64_t name[n]` as POINTER(c_int64); anything else is refused."""
+    m = re.fullmatch(r"([\w\s*]*?)(\w+)\s*(\[\d*\])?", decl)
+    if not m:
+        raise EbfiNativeError("include/ebfi_hip.h: %s: cannot bind parameter `%s`" % (func, decl))
+    base = " ".join(t for t in m.group(1).replace("*", " * ").split() if t != "const")
+    if m.group(3):
+        ctype = _c.POINTER(_i64) if base == "int64_t" else None
+    else:
+        ctype = _vp if "*" in base else _SCALARS.get(base)
+    if ctype is None:
+        raise EbfiNativeError("include/ebfi_hip.h: %s: parameter `%s` has no binding rule (`%s`)" % (func, m.group(2), decl))
+    return ctype
+
+
+def parse_header(text):
+    """(signatures, params, constants) of a C header text: {name: (restype, [argtypes])}, {name: [parameter declarations]}
+    and {NAME: int} of the enumerators and the `#define EBFI_* <integer>` lines.  A pure function of the text; whatever
+    it cannot bind by the rules above raises EbfiNativeError -- it never guesses and never skips a declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {k: int(v, 0) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(EBFI_\w+)[ \t]+(%s)[ \t]*$" % _INT, text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#ifdef __cplusplus.*?^[ \t]*#endif", " ", text, flags=re.S | re.M)      # extern "C" { ... }
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    def enum(m):
+        nxt = 0
+        for item in filter(None, (s.strip() for s in m.group(1).split(","))):
+            name, _, val = (s.strip() for s in item.partition("="))
+            if val and not re.fullmatch(_INT, val):
+                raise EbfiNativeError("include/ebfi_hip.h: enumerator %s: `%s` is not an integer literal" % (name, val))
+            nxt = constants[name] = int(val, 0) if val else nxt
+            nxt += 1
+        return " "
+    text = re.sub(r"(?:typedef\s+)?enum\s*\w*\s*\{([^}]*)\}\s*\w*\s*;", enum, text)
+
+    signatures, params = {}, {}
+    for stmt in filter(None, (" ".join(s.split()) for s in text.split(";"))):
+        m = re.fullmatch(r"([\w\s*]+?)\s*\b(\w+)\s*\((.*)\)", stmt)
+        if not m:
+            raise EbfiNativeError("include/ebfi_hip.h: cannot split `%s` into `ret name(params)`" % stmt)
+        ret, name, plist = " ".join(m.group(1).replace("*", " * ").split()), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise EbfiNativeError("include/ebfi_hip.h: %s: return type `%s` has no binding rule" % (name, ret))
+        decls = [] if plist == "void" else [p.strip() for p in plist.split(",")]
+        signatures[name] = (_RETURNS[ret], [_argtype(name, d) for d in decls])
+        params[name] = decls
+    return signatures, params, constants
+
+
+try:
+    with open(HEADER) as _f:
+        SIGNATURES, PARAMS, CONSTANTS = parse_header(_f.read())
+except OSError as e:
+    raise EbfiNativeError("cannot read the C header %s: %s" % (HEADER, e)) from e
+
+ABI_VERSION = CONSTANTS["EBFI_ABI_VERSION"]
+EBFI_F32, EBFI_F32_BF16MMA, EBFI_F32_BF16X3MMA = (CONSTANTS[k] for k in ("EBFI_F32", "EBFI_F32_BF16MMA", "EBFI_F32_BF16X3MMA"))
+EBFI_ERR_UNSUPPORTED = CONSTANTS["EBFI_ERR_UNSUPPORTED"]
 
 
 def declared_symbols():
-    """Function names declared in include/ebfi_hip.h (used by the export test)."""
+    """Function names declared in include/ebfi_hip.h: a crude name scan, deliberately independent of parse_header
+    (the tests hold the two against each other)."""
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(ebfi_[a-z0-9_]+)\s*\(", text)))
@@ -208,7 +129,7 @@ def build(verbose=False):
 def _counted(fn, name, n):
     def call(*a):
         if len(a) != n:
-            raise TypeError("%s takes %d arguments (include/ebfi_hip.h), %d given" % (name, n, len(a)))
+            raise TypeError("%s takes %d arguments (%s), %d given" % (name, n, ", ".join(PARAMS[name]) or "void", len(a)))
         return fn(*a)
     call.__name__ = name
     return call

@@ -19,6 +19,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import _native as N
+
 
 def is_distributed():
     """More than one rank -- or EBFI_FORCE_COLLECTIVES=1 with an initialised group of one: the collectives then run at
@@ -196,8 +198,8 @@ class FlatGradBucket:
 SUPPORTED_OPTIMIZERS = ("Adam", "AdamW", "SGD")
 # optimizer.args entries that say HOW a process runs the update, not what it computes: this process decides them
 _RUN_MODE_ARGS = ("foreach", "fused", "capturable")
-_OPTIM_ADAM, _OPTIM_SGD = 0, 1                                # include/ebfi_hip.h EBFI_OPTIM_*
-_OPTIM_DECOUPLED_DECAY, _OPTIM_AMSGRAD, _OPTIM_NESTEROV = 1, 2, 4
+_OPTIM_ADAM, _OPTIM_SGD, _OPTIM_DECOUPLED_DECAY, _OPTIM_AMSGRAD, _OPTIM_NESTEROV = (
+    N.CONSTANTS["EBFI_OPTIM_" + k] for k in ("ADAM", "SGD", "DECOUPLED_DECAY", "AMSGRAD", "NESTEROV"))
 
 
 def _refuse_group(name, group):

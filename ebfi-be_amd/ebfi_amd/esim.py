@@ -34,7 +34,7 @@ import torch
 
 from . import _native as N
 
-MAX_CHUNK = 128          # include/ebfi_hip.h EBFI_ESIM_MAX_CHUNK
+MAX_CHUNK = N.CONSTANTS["EBFI_ESIM_MAX_CHUNK"]
 MIN_THRESHOLD = 1e-3     # Cp / Cn below this are refused (the crossing loop's bound must stay small)
 
 

@@ -23,7 +23,7 @@ import torch
 
 from . import _native as N
 
-TABLE_MAX = 32          # include/ebfi_hip.h EBFI_NOISE_TABLE_MAX: the table travels by value in the kernel arguments
+TABLE_MAX = N.CONSTANTS["EBFI_NOISE_TABLE_MAX"]          # the table travels by value in the kernel arguments
 _MASK64 = (1 << 64) - 1
 
 
