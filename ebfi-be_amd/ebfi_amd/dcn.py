@@ -7,7 +7,14 @@ deformable_groups)``), and the modules ``DCNv2`` (:98-146), ``DCN`` (:149-194) a
 initialisation and the same argument checks as the extension wrappers
 (src/cuda/dcn_v2_cuda.cu:38-62,110-111).  Compute: ``ebfi_dcn_forward`` / ``ebfi_dcn_backward``.
 
-Not mirrored (out of scope): PS-ROI pooling and the ONNX wrapper.
+Deformable PS-ROI pooling (:230-435) likewise: the autograd op ``_DCNv2Pooling`` / ``dcn_v2_pooling`` (argument order
+``(input, rois, offset, spatial_scale, pooled_size, output_dim, no_trans, group_size, part_size, sample_per_part,
+trans_std)``) and the modules ``DCNv2Pooling`` and ``DCNPooling`` (``offset_mask_fc.*``).  Compute:
+``ebfi_dcn_pooling_forward`` / ``ebfi_dcn_pooling_backward``; the law and the two places where it is defined instead of
+reading out of bounds (``C == output_dim * group_size**2``, ROIs with a batch index outside the batch) are in
+include/ebfi_hip.h.
+
+Not mirrored (out of scope): the ONNX wrapper.
 """
 import logging
 import math
@@ -195,3 +202,186 @@ class DCN_sep(DCNv2, _SelfOffsetMixin):
         if not (offset.is_cuda and torch.cuda.is_current_stream_capturing()) and offset_mean > 100:
             logger.warning("Offset mean is {}, larger than 100.".format(offset_mean))
         return self._apply_op(input, offset, mask)
+
+
+# ------------------------------------------------------------------ deformable PS-ROI pooling
+def _pool_geometry(input, rois, trans, no_trans, output_dim, group_size, pooled_size, part_size, sample_per_part):
+    """Shape checks of both pooling passes; returns (B, C, H, W, R, nc)."""
+    if input.dim() != 4:
+        raise RuntimeError("input must be [B, C, H, W], got %s" % (tuple(input.shape),))
+    if rois.dim() != 2 or rois.shape[1] != 5:
+        raise RuntimeError("rois must be [R, 5] (batch index, x1, y1, x2, y2), got %s" % (tuple(rois.shape),))
+    B, C, H, W = (int(v) for v in input.shape)
+    R = int(rois.shape[0])
+    D, G, P, part, spp = int(output_dim), int(group_size), int(pooled_size), int(part_size), int(sample_per_part)
+    if min(B, C, H, W, D, G, P, part, spp) < 1:
+        raise RuntimeError("sizes must be >= 1: input %s, output_dim %d, group_size %d, pooled_size %d, part_size %d, "
+                           "sample_per_part %d" % (tuple(input.shape), D, G, P, part, spp))
+    if C != D * G * G:
+        raise RuntimeError("input channels must equal output_dim * group_size**2: %d vs %d * %d**2" % (C, D, G))
+    if no_trans:
+        nc = 1
+    else:
+        if trans.dim() != 4 or trans.shape[1] % 2 or trans.shape[1] < 2 or tuple(trans.shape[2:]) != (part, part):
+            raise RuntimeError("offset must be [>= %d, 2 * classes, %d, %d], got %s" % (R, part, part, tuple(trans.shape)))
+        if trans.shape[0] < R:
+            raise RuntimeError("offset has %d rows for %d rois" % (trans.shape[0], R))
+        nc = int(trans.shape[1]) // 2
+        if D % nc:
+            raise RuntimeError("output_dim %d is not a multiple of the %d classes of offset" % (D, nc))
+    return B, C, H, W, R, nc
+
+
+def _pool_require_gpu(**tensors):
+    for name, t in tensors.items():
+        if not t.is_cuda:
+            raise NotImplementedError("%s must be a GPU tensor: libebfi_hip.so has no CPU path" % name)
+
+
+def dcn_v2_pooling_forward(input, rois, trans, no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size,
+                           sample_per_part, trans_std):
+    """(output, count), both [R, output_dim, pooled_size, pooled_size]; `trans` may be the empty tensor when no_trans."""
+    no_trans = bool(no_trans)
+    if no_trans:
+        _pool_require_gpu(input=input, rois=rois)
+    else:
+        _pool_require_gpu(input=input, rois=rois, offset=trans)
+    B, C, H, W, R, nc = _pool_geometry(input, rois, trans, no_trans, output_dim, group_size, pooled_size, part_size,
+                                       sample_per_part)
+    # the reference reads these through raw data pointers after .contiguous(); be explicit too
+    input, rois = input.contiguous(), rois.contiguous()
+    trans = None if no_trans else trans.contiguous()
+    out = torch.empty((R, int(output_dim), int(pooled_size), int(pooled_size)), dtype=input.dtype, device=input.device)
+    count = torch.empty_like(out)
+    code = N.dtype_code(input)
+    with torch.cuda.device_of(input):
+        rc = N.lib().ebfi_dcn_pooling_forward(N.ptr(input), N.ptr(rois), N.ptr(trans), N.ptr(out), N.ptr(count),
+                                              B, C, H, W, R, nc, int(no_trans), float(spatial_scale), int(output_dim),
+                                              int(group_size), int(pooled_size), int(part_size), int(sample_per_part),
+                                              float(trans_std), code, N.stream_ptr(input.device))
+    N.check(rc, "ebfi_dcn_pooling_forward")
+    return out, count
+
+
+def dcn_v2_pooling_backward(grad_output, input, rois, trans, count, no_trans, spatial_scale, output_dim, group_size,
+                            pooled_size, part_size, sample_per_part, trans_std):
+    """(grad_input, grad_trans); grad_trans has the shape of `trans` (rows past the rois, and all of it when no_trans, 0)."""
+    no_trans = bool(no_trans)
+    if no_trans:
+        _pool_require_gpu(grad_output=grad_output, input=input, rois=rois, count=count)
+    else:
+        _pool_require_gpu(grad_output=grad_output, input=input, rois=rois, offset=trans, count=count)
+    B, C, H, W, R, nc = _pool_geometry(input, rois, trans, no_trans, output_dim, group_size, pooled_size, part_size,
+                                       sample_per_part)
+    oshape = (R, int(output_dim), int(pooled_size), int(pooled_size))
+    if tuple(grad_output.shape) != oshape or tuple(count.shape) != oshape:
+        raise RuntimeError("grad_output and count must be %s, got %s and %s" % (oshape, tuple(grad_output.shape),
+                                                                                tuple(count.shape)))
+    input, rois = input.contiguous(), rois.contiguous()
+    grad_output, count = grad_output.contiguous(), count.contiguous()
+    if R == 0:     # (the entry point writes nothing for an empty call)
+        return torch.zeros_like(input), (input.new_zeros(0) if no_trans else torch.zeros_like(trans))
+    gx = torch.empty_like(input)
+    if no_trans:
+        trans, gt, Rt = None, None, R
+    else:
+        trans = trans.contiguous()
+        gt, Rt = torch.empty_like(trans), int(trans.shape[0])
+    code = N.dtype_code(input)
+    with torch.cuda.device_of(input):
+        rc = N.lib().ebfi_dcn_pooling_backward(N.ptr(grad_output), N.ptr(input), N.ptr(rois), N.ptr(trans), N.ptr(count),
+                                               N.ptr(gx), N.ptr(gt), Rt, B, C, H, W, R, nc, int(no_trans),
+                                               float(spatial_scale), int(output_dim), int(group_size), int(pooled_size),
+                                               int(part_size), int(sample_per_part), float(trans_std), code,
+                                               N.stream_ptr(input.device))
+    N.check(rc, "ebfi_dcn_pooling_backward")
+    return gx, (gt if gt is not None else input.new_zeros(0))
+
+
+class _DCNv2Pooling(Function):
+    @staticmethod
+    def forward(ctx, input, rois, offset, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None,
+                sample_per_part=4, trans_std=0.0):
+        ctx.spatial_scale = spatial_scale
+        ctx.no_trans = int(no_trans)
+        ctx.output_dim = output_dim
+        ctx.group_size = group_size
+        ctx.pooled_size = pooled_size
+        ctx.part_size = pooled_size if part_size is None else part_size
+        ctx.sample_per_part = sample_per_part
+        ctx.trans_std = trans_std
+        output, output_count = dcn_v2_pooling_forward(input, rois, offset, ctx.no_trans, ctx.spatial_scale, ctx.output_dim,
+                                                      ctx.group_size, ctx.pooled_size, ctx.part_size, ctx.sample_per_part,
+                                                      ctx.trans_std)
+        ctx.save_for_backward(input, rois, offset, output_count)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        input, rois, offset, output_count = ctx.saved_tensors
+        grad_input, grad_offset = dcn_v2_pooling_backward(grad_output, input, rois, offset, output_count, ctx.no_trans,
+                                                          ctx.spatial_scale, ctx.output_dim, ctx.group_size,
+                                                          ctx.pooled_size, ctx.part_size, ctx.sample_per_part, ctx.trans_std)
+        if ctx.no_trans:
+            grad_offset = None
+        return grad_input, None, grad_offset, None, None, None, None, None, None, None, None
+
+
+dcn_v2_pooling = _DCNv2Pooling.apply
+
+
+class DCNv2Pooling(nn.Module):
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None, sample_per_part=4,
+                 trans_std=0.0):
+        super().__init__()
+        self.spatial_scale = spatial_scale
+        self.pooled_size = pooled_size
+        self.output_dim = output_dim
+        self.no_trans = no_trans
+        self.group_size = group_size
+        self.part_size = pooled_size if part_size is None else part_size
+        self.sample_per_part = sample_per_part
+        self.trans_std = trans_std
+
+    def _pool(self, input, rois, offset, no_trans):
+        return dcn_v2_pooling(input, rois, offset, self.spatial_scale, self.pooled_size, self.output_dim, no_trans,
+                              self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+
+    def forward(self, input, rois, offset):
+        # (the reference asserts C == output_dim and then indexes (d * G + gh) * G + gw: in bounds for group_size 1 only)
+        assert input.shape[1] == self.output_dim * self.group_size ** 2
+        if self.no_trans:
+            offset = input.new()
+        return self._pool(input, rois, offset, self.no_trans)
+
+
+class DCNPooling(DCNv2Pooling):
+    """Offsets and a mask from the ROI-aligned features themselves (dcn_v2.py:338-435): pool without offsets, run
+    offset_mask_fc (last layer zero-initialised), pool again with the offsets and multiply by sigmoid(mask)."""
+
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None, sample_per_part=4,
+                 trans_std=0.0, deform_fc_dim=1024):
+        super().__init__(spatial_scale, pooled_size, output_dim, no_trans, group_size, part_size, sample_per_part, trans_std)
+        self.deform_fc_dim = deform_fc_dim
+        if not no_trans:
+            self.offset_mask_fc = nn.Sequential(
+                nn.Linear(self.pooled_size * self.pooled_size * self.output_dim, self.deform_fc_dim),
+                nn.ReLU(inplace=True),
+                nn.Linear(self.deform_fc_dim, self.deform_fc_dim),
+                nn.ReLU(inplace=True),
+                nn.Linear(self.deform_fc_dim, self.pooled_size * self.pooled_size * 3))
+            self.offset_mask_fc[4].weight.data.zero_()
+            self.offset_mask_fc[4].bias.data.zero_()
+
+    def forward(self, input, rois):
+        assert input.shape[1] == self.output_dim * self.group_size ** 2
+        offset = input.new()
+        if self.no_trans:
+            return self._pool(input, rois, offset, self.no_trans)      # only roi_align
+        n = rois.shape[0]
+        roi = self._pool(input, rois, offset, True)
+        offset_mask = self.offset_mask_fc(roi.view(n, -1)).view(n, 3, self.pooled_size, self.pooled_size)
+        o1, o2, mask = torch.chunk(offset_mask, 3, dim=1)
+        offset = torch.cat((o1, o2), dim=1)
+        return self._pool(input, rois, offset, self.no_trans) * torch.sigmoid(mask)

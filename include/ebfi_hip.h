@@ -22,6 +22,9 @@
  *       pybind module `_ext`: dcn_v2_forward / dcn_v2_backward
  *       models/DCNv2/src/dcn_v2.h:9-92, src/vision.cpp:4-9, src/cuda/dcn_v2_cuda.cu:20-216,
  *       src/cuda/dcn_v2_im2col_cuda.cu:125-402
+ *   ebfi_dcn_pooling_forward / ebfi_dcn_pooling_backward
+ *       pybind module `_ext`: dcn_v2_psroi_pooling_forward / dcn_v2_psroi_pooling_backward
+ *       models/DCNv2/src/vision.cpp:7-8, src/cuda/dcn_v2_psroi_pooling_cuda.cu:58-419
  *   ebfi_conv2d_*               nn.Conv2d + activation inside ConvLayer (models/model_misc/submodules.py:159-200)
  *   ebfi_scale_residual_cat_*   exposure/time-scaled residual + concat of ResidualControl (model_singleframe.py:124-134)
  *   ebfi_prodmean_*             AdaptiveAvgPool2d(1) of a product of two maps (ExposureDecision, model_singleframe.py:66-68)
@@ -109,7 +112,8 @@ extern "C" {
  *      the training config), likewise; and ebfi_conv2d_backward_weight_f16g_multi_workspace /
  *      ebfi_conv2d_backward_weight_f16g_multi (the pure weight gradients of a training step, deferred and run in one launch) and
  *      ebfi_gather_sum_multi (their fold gathers), likewise; and ebfi_event_augment / ebfi_event_hot_pixels (the device noise
- *      law of the clip loaders), likewise */
+ *      law of the clip loaders), likewise; and ebfi_dcn_pooling_forward / _backward (the deformable PS-ROI pooling of the
+ *      DCNv2 package), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -191,6 +195,51 @@ int ebfi_dcn_backward(const void *input, const void *weight, const void *bias, c
                       int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw,
                       int ph, int pw, int dh, int dw, int deformable_group,
                       void *workspace, size_t workspace_bytes, int dtype, void *stream);
+
+/* ------------------------------------------------------------------ DCNv2 deformable PS-ROI pooling
+ * The second op of the reference's DCNv2 package (src/cuda/dcn_v2_psroi_pooling_cuda.cu).  Contiguous fp32:
+ *   input [B,C,H,W]   rois [R,5] = (batch index, x1, y1, x2, y2) in image pixels
+ *   trans [Rt >= R, 2*nc, part, part] (NULL when no_trans; nc is then 1)
+ *   output, count [R, D, P, P]  (D = output_dim, P = pooled_size; count = samples that contributed, as fp32)
+ * With G = group_size, spp = sample_per_part, cec = D / nc, every step ONE fp32 operation in this order (no fused
+ * multiply-add), for output element (n, d, ph, pw):
+ *   sw = round(x1) * scale - 0.5, ew = (round(x2) + 1) * scale - 0.5; sh, eh likewise   (C round(): half away from zero)
+ *   rw = max(ew - sw, 0.1f), bw = rw / P, sbw = bw / spp; rh, bh, sbh likewise
+ *   part_h = floor(float(ph) / P * part), part_w likewise; cls = d / cec
+ *   tx = trans[n, 2*cls, part_h, part_w] * trans_std, ty = trans[n, 2*cls + 1, ..] * trans_std   (0 when no_trans)
+ *   w0 = float(pw) * bw + sw, w0 += tx * rw; h0 likewise with ty * rh
+ *   gw = clamp(floor(float(pw) * G / P), 0, G - 1), gh likewise; the input channel is c = (d*G + gh)*G + gw
+ *   for ih, iw in [0, spp), ih outer: w = w0 + iw * sbw, h = h0 + ih * sbh
+ *       skipped when w < -0.5 || w > W - 0.5 || h < -0.5 || h > H - 0.5
+ *       else w = fmin(fmax(w, 0), W - 1), h likewise (a NaN coordinate becomes 0 and IS counted), and the sample is
+ *       the bilinear interpolation of plane c on the corners floor / ceil with dx = w - floor(w), dy = h - floor(h):
+ *       (1-dx)*(1-dy)*U00 + (1-dx)*dy*U01 + dx*(1-dy)*U10 + dx*dy*U11, Uxy = plane at column corner x and row corner y (0 = floor, 1 = ceil),
+ *       each product left to right, the four terms added left to right, the samples of a bin added in loop order from 0
+ *   output = count ? sum / count : 0
+ * Backward, dv = grad_output / count where count > 0: every included sample scatters q00, q01, q10, q11 times dv onto
+ * its four corners of grad_input, and adds to the x and y cells (n, cls, part_h, part_w) of grad_trans
+ *   (U11*dy + U10*(1-dy) - U01*dy - U00*(1-dy)) * trans_std * dv * rw   and
+ *   (U11*dx + U01*(1-dx) - U10*dx - U00*(1-dx)) * trans_std * dv * rh        (0 at an exactly integer coordinate).
+ * Two places where the reference reads out of bounds are defined instead:
+ *   - channels: the reference asserts C == D and indexes channel (d*G + gh)*G + gw, safe for G == 1 only.  Here
+ *     C == D * G * G is required (the reference's rule at G == 1, position-sensitive pooling otherwise), and D % nc == 0.
+ *   - batch index: an ROI whose batch index is not an integer value in [0, B) (NaN included) gives output = 0,
+ *     count = 0 and no gradient; the reference reads wherever the index points.
+ * count may be NULL in the forward.  grad_input [B,C,H,W] is zeroed by the library and accumulated with float atomics
+ * (last-bit run-to-run differences, like ebfi_dcn_backward); grad_trans [Rt, 2*nc, part, part] (NULL when no_trans) is
+ * zeroed whole -- rows R..Rt-1 stay 0 -- and every cell has ONE writer that sums in a fixed order: bit-reproducible.
+ * EBFI_F32 only.  Null pointers, sizes < 1 (R < 0, Rt < R), C != D*G*G, D % nc != 0, P / part / spp < 1 -> EBFI_ERR_ARG;
+ * spp > 32, or H * W beyond 2^31 - 1 -> EBFI_ERR_UNSUPPORTED; neither touches the GPU.  R == 0 is a no-op (nothing is written). */
+int ebfi_dcn_pooling_forward(const void *input, const void *rois, const void *trans, void *output, void *count,
+                             int B, int C, int H, int W, int R, int nc, int no_trans, float spatial_scale,
+                             int output_dim, int group_size, int pooled_size, int part_size, int sample_per_part,
+                             float trans_std, int dtype, void *stream);
+
+int ebfi_dcn_pooling_backward(const void *grad_output, const void *input, const void *rois, const void *trans,
+                              const void *count, void *grad_input, void *grad_trans, int Rt,
+                              int B, int C, int H, int W, int R, int nc, int no_trans, float spatial_scale,
+                              int output_dim, int group_size, int pooled_size, int part_size, int sample_per_part,
+                              float trans_std, int dtype, void *stream);
 
 /* ------------------------------------------------------------------ conv + bias + activation (ConvLayer)
  * What the reference gets from nn.Conv2d + nn.LeakyReLU / nn.Sigmoid inside ConvLayer
