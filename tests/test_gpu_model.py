@@ -363,6 +363,74 @@ def test_scale_residual_cat_kernel_pair():
             assert d.grad.shape == r.grad.shape and _rel(d.grad, r.grad) < 1e-5
 
 
+def _rel64(got, ref):
+    return ((got.detach().cpu().double() - ref).abs().max() / ref.abs().max()).item()
+
+
+# plane sizes 4 (one 16-byte vector), 12 (fewer vectors than lanes), 1028 (more than one sweep of 256 lanes, with a tail)
+STAGE_PLANES = [(2, 3, 1, 4), (1, 6, 3, 4), (2, 4, 4, 257)]
+
+
+@pytest.mark.parametrize("B,C,H,W", STAGE_PLANES)
+def test_scale_residual_cat_stage_vs_float64(B, C, H, W):
+    """csrc/fuse.hip against float64: the stage (`scale_residual_cat`) and its form without second scale and residual
+    (`scale_cat`: s1 and x absent), outputs within 1e-6 and every gradient within 1e-5 of max|ref|."""
+    from ebfi_amd.fused import scale_cat, scale_residual_cat
+    torch.manual_seed(17 + H * W)
+    cpu = [torch.randn(B, C, H, W), torch.randn(B, C, 1, 1), torch.randn(B, C, H, W), torch.randn(B, C, 1, 1), torch.randn(B, C, H, W)]
+    g = torch.randn(B, 2 * C, H, W)
+    for absent in (False, True):
+        a0, s0, a1, s1, x = [t.double().requires_grad_() for t in cpu]
+        ref = torch.cat([s0 * a0, a1], 1) if absent else torch.cat([s0 * a0 + x, s1 * a1 + x], 1)
+        ref.backward(g.double())
+        dev = [t.cuda().requires_grad_() for t in cpu]
+        out = scale_cat(dev[0], dev[1], dev[2]) if absent else scale_residual_cat(*dev)
+        assert type(out.grad_fn).__name__ == "_ScaleResidualCatBackward"                 # the native node, not torch's cat
+        out.backward(g.cuda())
+        assert out.shape == ref.shape and _rel64(out, ref.detach()) < 1e-6
+        pairs = [(dev[0], a0), (dev[1], s0), (dev[2], a1)] + ([] if absent else [(dev[3], s1), (dev[4], x)])
+        for d, r in pairs:
+            assert d.grad.shape == r.grad.shape and _rel64(d.grad, r.grad) < 1e-5
+        if absent:
+            assert dev[3].grad is None and dev[4].grad is None
+
+
+@pytest.mark.parametrize("B,C,H,W", STAGE_PLANES)
+def test_scale_residual_cat_ex_on_channel_halves_vs_float64(B, C, H, W):
+    """ebfi_scale_residual_cat_forward_ex / _backward_ex as rc_fused calls them: a0 / a1 are the two channel halves of one
+    [B, 2C, H, W] tensor (batch stride 2 * C * HW), the gradients of a0 / a1 leave as the halves of one tensor, and with
+    mask_leaky = 1 they leave multiplied by LeakyReLU'(a): against grad * LeakyReLU'(a) in float64."""
+    from ebfi_amd import _native as N
+    torch.manual_seed(23 + H * W)
+    slope, HW = 0.01, H * W
+    a, s0, s1 = torch.randn(B, 2 * C, H, W), torch.randn(B, C), torch.randn(B, C)
+    x, g = torch.randn(B, C, H, W), torch.randn(B, 2 * C, H, W)
+    a64, s064, s164, x64, g64 = (t.double() for t in (a, s0, s1, x, g))
+    k0, k1 = s064[:, :, None, None], s164[:, :, None, None]
+    ref = torch.cat([k0 * a64[:, :C] + x64, k1 * a64[:, C:] + x64], 1)
+    mask = torch.where(a64 > 0, torch.ones_like(a64), torch.full_like(a64, slope))
+    ref_ga = {0: g64 * torch.cat([k0.expand(B, C, H, W), k1.expand(B, C, H, W)], 1)}
+    ref_ga[1] = ref_ga[0] * mask
+    ref_gx = g64[:, :C] + g64[:, C:]
+    ref_gs0, ref_gs1 = (g64[:, :C] * a64[:, :C]).sum((2, 3)), (g64[:, C:] * a64[:, C:]).sum((2, 3))
+    ad, s0d, s1d, xd, gd = (t.cuda() for t in (a, s0, s1, x, g))
+    half = lambda t: N._vp(t.data_ptr() + 4 * C * HW)
+    lib, st = N.lib(), N.stream_ptr(ad.device)
+    out = torch.full((B, 2 * C, H, W), float("nan"), device="cuda")
+    N.check(lib.ebfi_scale_residual_cat_forward_ex(N.ptr(ad), N.ptr(s0d), half(ad), N.ptr(s1d), N.ptr(xd), N.ptr(out), B, C, HW,
+                                                   2 * C * HW, st), "ebfi_scale_residual_cat_forward_ex")
+    assert _rel64(out, ref) < 1e-6
+    for mask_leaky in (0, 1):
+        ga = torch.full((B, 2 * C, H, W), float("nan"), device="cuda")
+        gx = torch.full((B, C, H, W), float("nan"), device="cuda")
+        gs0, gs1 = torch.full((B, C), float("nan"), device="cuda"), torch.full((B, C), float("nan"), device="cuda")
+        N.check(lib.ebfi_scale_residual_cat_backward_ex(N.ptr(gd), N.ptr(ad), N.ptr(s0d), half(ad), N.ptr(s1d), N.ptr(ga), half(ga),
+                                                        N.ptr(gx), N.ptr(gs0), N.ptr(gs1), B, C, HW, 2 * C * HW, 2 * C * HW, mask_leaky,
+                                                        slope, st), "ebfi_scale_residual_cat_backward_ex")
+        assert _rel64(ga, ref_ga[mask_leaky]) < 1e-5 and _rel64(gx, ref_gx) < 1e-5
+        assert _rel64(gs0, ref_gs0) < 1e-5 and _rel64(gs1, ref_gs1) < 1e-5
+
+
 def test_full_size_modes_agree_and_batch_is_independent():
     """BASELINE size (B=8, 256x256, default widths): the split-precision mode against the exact fp32 mode on the same
     weights and inputs -- outputs within 1e-3, the packed gradient within 1e-2 in norm -- and sample independence:
