@@ -197,6 +197,150 @@ __global__ __launch_bounds__(256) void sgd_opt_kernel(float *__restrict__ p, con
         }
 }
 
+// ebfi_optim_step_ex: the same laws with a gradient scale (the clipping coefficient ebfi_grad_norm left on the device) in front
+// and an exponential moving average of the parameters behind, still ONE launch: the scale costs no map (one word, `g` stays
+// read-only: the scaled gradient lives in registers only), the average two (e read + written).  Continuing the list above,
+// contraction off:
+//   g' = g * s  (s = grad_scale[0], or 1 without one: x * 1 is x, bit for bit) BEFORE the L2 fma, as clipping precedes
+//   the optimiser in torch;  <the update above on g'>;  e <- e + w * (p_new - e),  w = (float)(1 - d),
+//   d = ema_decay | min(ema_decay, (1 + t) / (10 + t)) (warm-up), t = ema_step[0] in double
+// adam_elem / sgd_elem are the functions the kernels above inline, so a scale s gives the bits ebfi_optim_step gives on a
+// gradient multiplied by s in float32 beforehand.  The guard protocol is optim_skipped's, word for word, extended to the
+// average: a skipped step takes ema_step back too, writes no e, and counts once in guard[1].
+struct EmaArgs {
+    double decay;
+    int warmup;
+};
+
+__device__ __forceinline__ float scaled(float gg, float s) {
+#pragma clang fp contract(off)
+    return gg * s;
+}
+
+__device__ __forceinline__ void ema_elem(float &ee, float pp, float w) {
+#pragma clang fp contract(off)
+    const float d = pp - ee;
+    ee = ee + w * d;
+}
+
+__device__ __forceinline__ float ema_weight(const float *__restrict__ ema_step, const EmaArgs &ea) {
+    double d = ea.decay;
+    if (ea.warmup) {
+        const double t = (double)ema_step[0];
+        const double ramp = (1.0 + t) / (10.0 + t);
+        d = ramp < d ? ramp : d;
+    }
+    return (float)(1.0 - d);
+}
+
+__device__ __forceinline__ bool optim_skipped_ex(float *__restrict__ step, float *__restrict__ ema_step, int *__restrict__ guard,
+                                                 const float *__restrict__ flag) {
+    if (guard != nullptr) {
+        const bool by_flag = flag != nullptr && !(flag[0] == 0.f);
+        if (guard[0] != 0 || by_flag) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) {
+                if (step != nullptr) step[0] -= 1.f;
+                if (ema_step != nullptr) ema_step[0] -= 1.f;
+                guard[1] += 1;
+                if (by_flag) guard[0] = 1;
+            }
+            return true;
+        }
+    }
+    return false;
+}
+
+template <int WD, bool AMS, bool EMA>
+__global__ __launch_bounds__(256) void adam_ex_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                      float *__restrict__ v, float *__restrict__ vmax, float *__restrict__ step,
+                                                      int64_t n4, int64_t n, OptimArgs a, int *__restrict__ guard,
+                                                      const float *__restrict__ flag, const float *__restrict__ grad_scale,
+                                                      float *__restrict__ ema, float *__restrict__ ema_step, EmaArgs ea) {
+    if (optim_skipped_ex(step, EMA ? ema_step : nullptr, guard, flag)) return;
+    const double t = (double)step[0];
+    const double c1 = 1.0 - pow(a.beta1, t), c2 = 1.0 - pow(a.beta2, t);
+    AdamCoef c;
+    c.step_size = (float)(a.lr / c1), c.c2s = (float)sqrt(c2);
+    c.w1 = (float)(1.0 - a.beta1), c.b2 = (float)a.beta2, c.w2 = (float)(1.0 - a.beta2), c.eps = (float)a.eps;
+    c.wd = (float)a.weight_decay, c.keep = (float)(1.0 - a.lr * a.weight_decay);
+    const float s = grad_scale != nullptr ? grad_scale[0] : 1.f;
+    const float w = EMA ? ema_weight(ema_step, ea) : 0.f;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n4) {
+        float4 P = reinterpret_cast<float4 *>(p)[i], M = reinterpret_cast<float4 *>(m)[i], V = reinterpret_cast<float4 *>(v)[i];
+        const float4 G = reinterpret_cast<const float4 *>(g)[i];
+        float4 X = make_float4(0.f, 0.f, 0.f, 0.f), E = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (AMS) X = reinterpret_cast<float4 *>(vmax)[i];
+        if (EMA) E = reinterpret_cast<float4 *>(ema)[i];
+        adam_elem<WD, AMS>(P.x, scaled(G.x, s), M.x, V.x, X.x, c);
+        adam_elem<WD, AMS>(P.y, scaled(G.y, s), M.y, V.y, X.y, c);
+        adam_elem<WD, AMS>(P.z, scaled(G.z, s), M.z, V.z, X.z, c);
+        adam_elem<WD, AMS>(P.w, scaled(G.w, s), M.w, V.w, X.w, c);
+        reinterpret_cast<float4 *>(p)[i] = P;
+        reinterpret_cast<float4 *>(m)[i] = M;
+        reinterpret_cast<float4 *>(v)[i] = V;
+        if (AMS) reinterpret_cast<float4 *>(vmax)[i] = X;
+        if (EMA) {
+            ema_elem(E.x, P.x, w);
+            ema_elem(E.y, P.y, w);
+            ema_elem(E.z, P.z, w);
+            ema_elem(E.w, P.w, w);
+            reinterpret_cast<float4 *>(ema)[i] = E;
+        }
+    }
+    if (i == 0)
+        for (int64_t k = n4 * 4; k < n; ++k) {
+            float x = 0.f;
+            if (AMS) x = vmax[k];
+            adam_elem<WD, AMS>(p[k], scaled(g[k], s), m[k], v[k], x, c);
+            if (AMS) vmax[k] = x;
+            if (EMA) ema_elem(ema[k], p[k], w);
+        }
+}
+
+template <int WD, int MOM, bool EMA>
+__global__ __launch_bounds__(256) void sgd_ex_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ buf,
+                                                     float *__restrict__ step, int64_t n4, int64_t n, OptimArgs a,
+                                                     int *__restrict__ guard, const float *__restrict__ flag,
+                                                     const float *__restrict__ grad_scale, float *__restrict__ ema,
+                                                     float *__restrict__ ema_step, EmaArgs ea) {
+    if (optim_skipped_ex(step, EMA ? ema_step : nullptr, guard, flag)) return;
+    SgdCoef c;
+    c.neg_lr = (float)(-a.lr), c.wd = (float)a.weight_decay, c.mom = (float)a.momentum, c.undamp = (float)(1.0 - a.dampening);
+    c.first = MOM != MOM_NONE && step[0] == 1.f;
+    const float s = grad_scale != nullptr ? grad_scale[0] : 1.f;
+    const float w = EMA ? ema_weight(ema_step, ea) : 0.f;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n4) {
+        float4 P = reinterpret_cast<float4 *>(p)[i];
+        const float4 G = reinterpret_cast<const float4 *>(g)[i];
+        float4 B = make_float4(0.f, 0.f, 0.f, 0.f), E = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (MOM != MOM_NONE) B = reinterpret_cast<float4 *>(buf)[i];
+        if (EMA) E = reinterpret_cast<float4 *>(ema)[i];
+        sgd_elem<WD, MOM>(P.x, scaled(G.x, s), B.x, c);
+        sgd_elem<WD, MOM>(P.y, scaled(G.y, s), B.y, c);
+        sgd_elem<WD, MOM>(P.z, scaled(G.z, s), B.z, c);
+        sgd_elem<WD, MOM>(P.w, scaled(G.w, s), B.w, c);
+        reinterpret_cast<float4 *>(p)[i] = P;
+        if (MOM != MOM_NONE) reinterpret_cast<float4 *>(buf)[i] = B;
+        if (EMA) {
+            ema_elem(E.x, P.x, w);
+            ema_elem(E.y, P.y, w);
+            ema_elem(E.z, P.z, w);
+            ema_elem(E.w, P.w, w);
+            reinterpret_cast<float4 *>(ema)[i] = E;
+        }
+    }
+    if (i == 0)
+        for (int64_t k = n4 * 4; k < n; ++k) {
+            float b = 0.f;
+            if (MOM != MOM_NONE) b = buf[k];
+            sgd_elem<WD, MOM>(p[k], scaled(g[k], s), b, c);
+            if (MOM != MOM_NONE) buf[k] = b;
+            if (EMA) ema_elem(ema[k], p[k], w);
+        }
+}
+
 // Gradient packing of the training step (ebfi_amd.dp.FlatGradBucket.gather): the per-parameter gradient tensors autograd
 // produced are copied into the one flat buffer the all-reduce and the Adam launch work on.  The source pointers travel BY VALUE
 // in the kernel arguments, 128 tensors per launch (3 launches for the model's 255 parameters) -- nothing to upload, and a
@@ -420,4 +564,108 @@ extern "C" int ebfi_optim_step(int kind, int flags, float *param, const float *g
     EBFI_SGD_CASE(WD_L2, MOM_NESTEROV, "optim_sgd_l2_nesterov");
 #undef EBFI_SGD_CASE
     return check_launch("optim_sgd");
+}
+
+namespace {
+
+template <int WD, bool AMS, bool EMA>
+void launch_adam_ex(const char *label, double maps, float *p, const float *g, float *m, float *v, float *vmax, float *step,
+                    int64_t n, const OptimArgs &a, int *guard, const float *flag, const float *grad_scale, float *ema,
+                    float *ema_step, const EmaArgs &ea, hipStream_t st) {
+    const int64_t n4 = n / 4;
+    ProfScope ps(label, st, 0.0, maps * 4.0 * (double)n);
+    hipLaunchKernelGGL((adam_ex_kernel<WD, AMS, EMA>), dim3((unsigned)ceil_div(std::max<int64_t>(n4, 1), 256)), dim3(256), 0, st, p,
+                       g, m, v, vmax, step, n4, n, a, guard, flag, grad_scale, ema, ema_step, ea);
+}
+
+template <int WD, int MOM, bool EMA>
+void launch_sgd_ex(const char *label, double maps, float *p, const float *g, float *buf, float *step, int64_t n,
+                   const OptimArgs &a, int *guard, const float *flag, const float *grad_scale, float *ema, float *ema_step,
+                   const EmaArgs &ea, hipStream_t st) {
+    const int64_t n4 = n / 4;
+    ProfScope ps(label, st, 0.0, maps * 4.0 * (double)n);
+    hipLaunchKernelGGL((sgd_ex_kernel<WD, MOM, EMA>), dim3((unsigned)ceil_div(std::max<int64_t>(n4, 1), 256)), dim3(256), 0, st, p,
+                       g, buf, step, n4, n, a, guard, flag, grad_scale, ema, ema_step, ea);
+}
+
+}  // namespace
+
+extern "C" int ebfi_optim_step_ex(int kind, int flags, float *param, const float *grad, float *state0, float *state1, float *state2,
+                                  float *step, int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                  double momentum, double dampening, int *guard, const float *flag, const float *grad_scale,
+                                  float *ema, float *ema_step, double ema_decay, int ema_warmup, void *stream) {
+    if (!grad_scale && !ema)                                            // nothing to add: the launch it has always been
+        return ebfi_optim_step(kind, flags, param, grad, state0, state1, state2, step, n, lr, beta1, beta2, eps, weight_decay,
+                               momentum, dampening, guard, flag, stream);
+    if (kind != EBFI_OPTIM_ADAM && kind != EBFI_OPTIM_SGD)
+        return fail(EBFI_ERR_UNSUPPORTED, "optim_step_ex: unknown optimiser kind %d", kind);
+    const int known = kind == EBFI_OPTIM_ADAM ? (EBFI_OPTIM_DECOUPLED_DECAY | EBFI_OPTIM_AMSGRAD) : EBFI_OPTIM_NESTEROV;
+    if (flags & ~known) return fail(EBFI_ERR_ARG, "optim_step_ex: option flags 0x%x do not belong to optimiser kind %d", flags, kind);
+    if (!(weight_decay >= 0.0)) return fail(EBFI_ERR_ARG, "optim_step_ex: weight_decay must not be negative");
+    if (flag && !guard) return fail(EBFI_ERR_ARG, "optim_step_ex: an overflow flag needs the guard words");
+    if (!param || !grad || n < 0) return fail(EBFI_ERR_ARG, "optim_step_ex: null argument");
+    if (!aligned16(param) || !aligned16(grad)) return fail(EBFI_ERR_ARG, "optim_step_ex: buffers must be 16-byte aligned");
+    if (ema) {
+        if (!ema_step) return fail(EBFI_ERR_ARG, "optim_step_ex: the moving average needs its step word");
+        if (!aligned16(ema)) return fail(EBFI_ERR_ARG, "optim_step_ex: buffers must be 16-byte aligned");
+        if (!(ema_decay >= 0.0 && ema_decay < 1.0))
+            return fail(EBFI_ERR_ARG, "optim_step_ex: ema_decay must lie in [0, 1), got %g", ema_decay);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const OptimArgs a{lr, beta1, beta2, eps, weight_decay, momentum, dampening};
+    const EmaArgs ea{ema_decay, ema_warmup != 0 ? 1 : 0};
+    const bool avg = ema != nullptr;
+    const double extra = avg ? 2.0 : 0.0;
+    if (kind == EBFI_OPTIM_ADAM) {
+        const bool ams = (flags & EBFI_OPTIM_AMSGRAD) != 0, decoupled = (flags & EBFI_OPTIM_DECOUPLED_DECAY) != 0;
+        if (!state0 || !state1 || !step || (ams && !state2))
+            return fail(EBFI_ERR_ARG, "optim_step_ex: Adam needs exp_avg, exp_avg_sq%s and the step word", ams ? ", max_exp_avg_sq" : "");
+        if (!aligned16(state0) || !aligned16(state1) || (ams && !aligned16(state2)))
+            return fail(EBFI_ERR_ARG, "optim_step_ex: buffers must be 16-byte aligned");
+        if (n == 0) return EBFI_OK;
+        const int wd = weight_decay == 0.0 ? WD_NONE : decoupled ? WD_DECOUPLED : WD_L2;
+        const double maps = (ams ? 9.0 : 7.0) + extra;
+#define EBFI_ADAM_EX_CASE(W, A, L)                                                                                               \
+    if (wd == W && ams == A) {                                                                                                   \
+        if (avg) launch_adam_ex<W, A, true>(L "_ema", maps, param, grad, state0, state1, state2, step, n, a, guard, flag,       \
+                                            grad_scale, ema, ema_step, ea, st);                                                  \
+        else launch_adam_ex<W, A, false>(L, maps, param, grad, state0, state1, state2, step, n, a, guard, flag, grad_scale,     \
+                                         nullptr, nullptr, ea, st);                                                              \
+    }
+        EBFI_ADAM_EX_CASE(WD_NONE, false, "optim_ex_adam")
+        EBFI_ADAM_EX_CASE(WD_L2, false, "optim_ex_adam_l2")
+        EBFI_ADAM_EX_CASE(WD_DECOUPLED, false, "optim_ex_adamw")
+        EBFI_ADAM_EX_CASE(WD_NONE, true, "optim_ex_adam_ams")
+        EBFI_ADAM_EX_CASE(WD_L2, true, "optim_ex_adam_l2_ams")
+        EBFI_ADAM_EX_CASE(WD_DECOUPLED, true, "optim_ex_adamw_ams")
+#undef EBFI_ADAM_EX_CASE
+        return check_launch("optim_ex_adam");
+    }
+    const bool nesterov = (flags & EBFI_OPTIM_NESTEROV) != 0;
+    if (!(momentum >= 0.0)) return fail(EBFI_ERR_ARG, "optim_step_ex: momentum must not be negative");
+    if (nesterov && (momentum <= 0.0 || dampening != 0.0))
+        return fail(EBFI_ERR_ARG, "optim_step_ex: Nesterov momentum requires a momentum and zero dampening");
+    const int mom = momentum == 0.0 ? MOM_NONE : nesterov ? MOM_NESTEROV : MOM_PLAIN;
+    if (mom != MOM_NONE && (!state0 || !step))
+        return fail(EBFI_ERR_ARG, "optim_step_ex: SGD with momentum needs the momentum buffer and the step word");
+    if (mom != MOM_NONE && !aligned16(state0)) return fail(EBFI_ERR_ARG, "optim_step_ex: buffers must be 16-byte aligned");
+    if (n == 0) return EBFI_OK;
+    const int wd = weight_decay == 0.0 ? WD_NONE : WD_L2;
+    const double maps = (mom == MOM_NONE ? 3.0 : 5.0) + extra;
+    float *word = mom == MOM_NONE ? nullptr : step;      // (plain SGD keeps no count: its kernel never reads one)
+#define EBFI_SGD_EX_CASE(W, M, L)                                                                                                \
+    if (wd == W && mom == M) {                                                                                                   \
+        if (avg) launch_sgd_ex<W, M, true>(L "_ema", maps, param, grad, state0, word, n, a, guard, flag, grad_scale, ema,       \
+                                           ema_step, ea, st);                                                                    \
+        else launch_sgd_ex<W, M, false>(L, maps, param, grad, state0, word, n, a, guard, flag, grad_scale, nullptr, nullptr, ea, \
+                                        st);                                                                                     \
+    }
+    EBFI_SGD_EX_CASE(WD_NONE, MOM_NONE, "optim_ex_sgd")
+    EBFI_SGD_EX_CASE(WD_L2, MOM_NONE, "optim_ex_sgd_l2")
+    EBFI_SGD_EX_CASE(WD_NONE, MOM_PLAIN, "optim_ex_sgd_mom")
+    EBFI_SGD_EX_CASE(WD_L2, MOM_PLAIN, "optim_ex_sgd_l2_mom")
+    EBFI_SGD_EX_CASE(WD_NONE, MOM_NESTEROV, "optim_ex_sgd_nesterov")
+    EBFI_SGD_EX_CASE(WD_L2, MOM_NESTEROV, "optim_ex_sgd_l2_nesterov")
+#undef EBFI_SGD_EX_CASE
+    return check_launch("optim_ex_sgd");
 }

@@ -232,6 +232,55 @@ def optimizer_arguments(name, args=None):
     return args
 
 
+_NORM_L2, _NORM_INF = N.CONSTANTS["EBFI_NORM_L2"], N.CONSTANTS["EBFI_NORM_INF"]
+
+
+def clip_arguments(clip):
+    """Validate a gradient-clipping setting without touching a device -> (max_norm, norm_type) with norm_type 2.0 or inf, or None.
+    `clip`: None, (max_norm, norm_type), {"max_norm": ..., "norm_type": ...} (norm_type defaults to 2) or a bare number."""
+    if clip is None:
+        return None
+    if isinstance(clip, dict):
+        unknown = set(clip) - {"max_norm", "norm_type"}
+        if unknown or "max_norm" not in clip:
+            raise ValueError("clip_grad takes max_norm and norm_type, got %r" % (sorted(clip),))
+        clip = (clip["max_norm"], clip.get("norm_type", 2))
+    elif isinstance(clip, (int, float)):
+        clip = (clip, 2)
+    try:
+        max_norm, norm_type = clip
+        max_norm, norm_type = float(max_norm), float(norm_type)
+    except (TypeError, ValueError) as e:
+        raise ValueError("clip_grad must be (max_norm, norm_type), got %r" % (clip,)) from e
+    if not (max_norm > 0.0 and max_norm != float("inf")):
+        raise ValueError("clip_grad: max_norm must be a positive finite number, got %r" % (max_norm,))
+    if norm_type not in (2.0, float("inf")):
+        raise ValueError("clip_grad: norm_type must be 2 or inf (the total norms the native reduction implements), got %r" % (norm_type,))
+    return max_norm, norm_type
+
+
+def ema_arguments(ema):
+    """Validate a weight-average setting without touching a device -> (decay, warmup) or None.
+    `ema`: None, (decay, warmup), {"decay": ..., "warmup": ...} (warmup defaults to False; other keys, such as the trainers'
+    `validate`, are not this function's) or a bare decay."""
+    if ema is None:
+        return None
+    if isinstance(ema, dict):
+        if "decay" not in ema:
+            raise ValueError("ema needs a decay, got %r" % (sorted(ema),))
+        ema = (ema["decay"], ema.get("warmup", False))
+    elif isinstance(ema, (int, float)):
+        ema = (ema, False)
+    try:
+        decay, warmup = ema
+        decay, warmup = float(decay), bool(warmup)
+    except (TypeError, ValueError) as e:
+        raise ValueError("ema must be (decay, warmup), got %r" % (ema,)) from e
+    if not (0.0 <= decay < 1.0):
+        raise ValueError("ema: decay must lie in [0, 1), got %r" % (decay,))
+    return decay, warmup
+
+
 class FlatOptimizer:
     """torch.optim.Adam, AdamW or SGD over ONE flat parameter buffer.
 
@@ -240,10 +289,25 @@ class FlatOptimizer:
     launch over 5.7 M elements (csrc/optim.hip) instead of a multi-tensor pass over 255 tensors.  `inner` is
     ``getattr(torch.optim, name)([flat], **args)``: it owns hyper-parameters and state, torch's defaults and constructor
     checks apply, and LR schedulers work on it.  `state_dict()` / `load_state_dict()` speak torch's per-parameter layout
-    of that class -- what the reference's checkpoints hold (train_ours.py:621-671) -- so checkpoints stay interchangeable."""
+    of that class -- what the reference's checkpoints hold (train_ours.py:621-671) -- so checkpoints stay interchangeable.
 
-    def __init__(self, params, name="Adam", **args):
+    clip = (max_norm, norm_type), norm_type 2 or inf: torch.nn.utils.clip_grad_norm_ over all parameters, without its 255
+    per-tensor norms, its host-visible scalar and its in-place scaling.  `step()` launches the norm of the packed gradient
+    (csrc/gradnorm.hip: float64 accumulation in a fixed order -- every rank of a job computes the same bits from the same
+    all-reduced buffer) and the update reads the coefficient on the device as its gradient scale.  After a step
+    `last_grad_norm` is a float32[2] tensor on the parameters' device, [total norm, coefficient]; the step never reads it back.
+    The gradient buffer is only read: `param.grad` and `FlatGradBucket.flat` keep the UNCLIPPED averaged gradient (the
+    `grad_norm/` layer statistics of the training monitor therefore show unclipped norms; `grad_norm/total` and
+    `grad_norm/clip_coef` say what the update made of them).
+    ema = (decay, warmup): `ema_flat`, a buffer beside the parameters that starts as their copy and follows every APPLIED step
+    with e <- e + (1 - d)(p - e) in the update's own launch; d = decay, or min(decay, (1 + t) / (10 + t)) with warm-up, t =
+    `ema_step` (a device word: a step skipped by the overflow guard neither moves the average nor counts).
+    Both are off by default, and with both off `step()` launches exactly what it launched without them.  CPU tensors (host
+    tests, gloo rehearsals) take the same laws in torch operations on a temporary."""
+
+    def __init__(self, params, name="Adam", clip=None, ema=None, **args):
         args = optimizer_arguments(name, args)
+        self.clip, self.ema = clip_arguments(clip), ema_arguments(ema)
         self.name = name
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
@@ -260,10 +324,74 @@ class FlatOptimizer:
         # SGD with momentum on the device: 0 until the first APPLIED step (the overflow guard takes a skipped one back), so
         # the kernel knows when `buf <- d` holds.  Private: torch's SGD state has no step and the exported state shows none.
         self._sgd_step = None
+        self.last_grad_norm = self._norm_workspace = None
+        self.ema_flat = self.ema_step = None
+        if self.clip is not None:
+            self.last_grad_norm = torch.tensor([0.0, 1.0], dtype=torch.float32, device=flat.device)
+        if self.ema is not None:
+            self.ema_flat = flat.detach().clone()
+            self.ema_step = torch.zeros((), dtype=torch.float32, device=flat.device)
 
     @property
     def param_groups(self):
         return self.inner.param_groups
+
+    # ------------------------------------------------------------------------------------------------ clipping / average
+    def _native_norm(self, flat_grad):
+        """The two norm launches on the packed gradient -> last_grad_norm (overwritten in place: a ring may copy from it)."""
+        max_norm, norm_type = self.clip
+        n = flat_grad.numel()
+        need = N.lib().ebfi_grad_norm_workspace(n)
+        if self._norm_workspace is None or self._norm_workspace.numel() * 8 < need:
+            self._norm_workspace = torch.empty(max(1, need // 8), dtype=torch.float64, device=flat_grad.device)
+        with torch.cuda.device_of(flat_grad):
+            rc = N.lib().ebfi_grad_norm(N.ptr(flat_grad), n, _NORM_INF if norm_type == float("inf") else _NORM_L2, max_norm,
+                                        N.ptr(self.last_grad_norm), N.ptr(self._norm_workspace), self._norm_workspace.numel() * 8,
+                                        N.stream_ptr(flat_grad.device))
+        N.check(rc, "ebfi_grad_norm")
+
+    def _host_norm(self, flat_grad):
+        """The same two numbers in torch operations (CPU tensors): float64 norm, float32 coefficient."""
+        max_norm, norm_type = self.clip
+        g = flat_grad.detach().double()
+        if g.numel() == 0:
+            self.last_grad_norm.copy_(torch.tensor([0.0, 1.0]))
+            return
+        norm = (g.abs().max() if norm_type == float("inf") else (g * g).sum().sqrt()).float()
+        coef = torch.tensor(max_norm, dtype=torch.float32) / (norm + torch.tensor(1e-6, dtype=torch.float32))
+        coef = torch.where(coef > 1.0, torch.ones_like(coef), coef)            # (a NaN stays)
+        self.last_grad_norm.copy_(torch.stack([norm, coef]))
+
+    def _host_average(self):
+        """One applied average in torch operations (CPU tensors), every operation rounded to float32 once."""
+        decay, warmup = self.ema
+        self.ema_step += 1
+        t = float(self.ema_step)
+        d = min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+        w = float(torch.tensor(1.0 - d, dtype=torch.float64).float())
+        delta = self.flat.detach() - self.ema_flat
+        self.ema_flat.add_(delta.mul_(w))
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """Start the average again from the current parameters (a loaded model without an average of its own)."""
+        if self.ema is not None:
+            self.ema_flat.copy_(self.flat.detach())
+            self.ema_step.zero_()
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange the CONTENTS of the parameter buffer and the average (addresses, views and the graphs that hold them stay):
+        the model then computes with the averaged weights.  A second call restores both, bit for bit."""
+        if self.ema is None:
+            raise ValueError("this optimiser keeps no moving average of the weights (ema=None)")
+        keep = self.flat.detach().clone()
+        self.flat.data.copy_(self.ema_flat)
+        self.ema_flat.copy_(keep)
+
+    def ema_views(self):
+        """The average in the shapes of `params`, as views of `ema_flat`."""
+        return [self.ema_flat[sl].view_as(p) for _, p, sl in self._slices()]
 
     def step(self, flat_grad, guard=None, flag=None):
         """`flat_grad`: the packed gradient in the order of `params` (FlatGradBucket.flat).  `guard`: int32[2] tensor of
@@ -277,15 +405,21 @@ class FlatOptimizer:
         if self._native_step(flat_grad, guard, flag):
             return
         _refuse_group(self.name, self.inner.param_groups[0])
+        if self.clip is not None:
+            self._host_norm(flat_grad)
         if guard is not None:                                     # torch's own step (CPU tensors): host-side check
             if flag is not None and not float(flag[0]) == 0.0:
                 guard[0] = 1
             if int(guard[0].item()) != 0:
                 guard[1] += 1
                 return
-        self.flat.grad = flat_grad
+        # (the scaled gradient is a temporary: the packed buffer keeps the unclipped values, as on the device)
+        self.flat.grad = flat_grad if self.clip is None else flat_grad * self.last_grad_norm[1]
         self.inner.step()
         self.flat.grad = None
+        if self.ema is not None:
+            with torch.no_grad():
+                self._host_average()
 
     def _native_step(self, flat_grad, guard=None, flag=None):
         """The update as ONE bandwidth-bound launch of libebfi_hip.so (csrc/optim.hip, ebfi_optim_step) on the state tensors
@@ -332,12 +466,27 @@ class FlatOptimizer:
             hook(opt, (), {})
         if word is not None:
             word += 1
-        with torch.cuda.device_of(self.flat):
-            rc = N.lib().ebfi_optim_step(kind, flags, N.ptr(self.flat.data), N.ptr(flat_grad), N.ptr(states[0]), N.ptr(states[1]),
-                                         N.ptr(states[2]), N.ptr(word), self.flat.numel(), float(grp["lr"]), float(b1), float(b2),
-                                         float(eps), float(grp["weight_decay"]), momentum, dampening, N.ptr(guard), N.ptr(flag),
-                                         N.stream_ptr(dev))
-        N.check(rc, "ebfi_optim_step")
+        hyper = (float(grp["lr"]), float(b1), float(b2), float(eps), float(grp["weight_decay"]), momentum, dampening)
+        if self.clip is None and self.ema is None:                # the default: the one launch it has always been
+            with torch.cuda.device_of(self.flat):
+                rc = N.lib().ebfi_optim_step(kind, flags, N.ptr(self.flat.data), N.ptr(flat_grad), N.ptr(states[0]), N.ptr(states[1]),
+                                             N.ptr(states[2]), N.ptr(word), self.flat.numel(), *hyper, N.ptr(guard), N.ptr(flag),
+                                             N.stream_ptr(dev))
+            N.check(rc, "ebfi_optim_step")
+        else:
+            scale = None
+            if self.clip is not None:
+                self._native_norm(flat_grad)
+                scale = self.last_grad_norm[1:2]
+            decay, warmup = self.ema if self.ema is not None else (0.0, False)
+            if self.ema is not None:
+                self.ema_step += 1
+            with torch.cuda.device_of(self.flat):
+                rc = N.lib().ebfi_optim_step_ex(kind, flags, N.ptr(self.flat.data), N.ptr(flat_grad), N.ptr(states[0]),
+                                                N.ptr(states[1]), N.ptr(states[2]), N.ptr(word), self.flat.numel(), *hyper,
+                                                N.ptr(guard), N.ptr(flag), N.ptr(scale), N.ptr(self.ema_flat), N.ptr(self.ema_step),
+                                                decay, int(warmup), N.stream_ptr(dev))
+            N.check(rc, "ebfi_optim_step_ex")
         opt._opt_called = True
         if hasattr(opt, "_step_count"):
             opt._step_count += 1
@@ -434,23 +583,23 @@ class FlatOptimizer:
         self.inner.state[self.flat] = dict(bufs, step=step)
 
 
-def build_flat_optimizer(params, optimizer=None, lr=1e-4, betas=(0.9, 0.999)):
+def build_flat_optimizer(params, optimizer=None, lr=1e-4, betas=(0.9, 0.999), clip=None, ema=None):
     """The engines' optimiser: None -> FlatAdam(lr, betas), exactly what they have always built; otherwise the config's
     optimizer section {"name": ..., "args": {...}}, with the `lr=` / `betas=` keywords filling in what args leaves out
-    (betas only where the class has them)."""
+    (betas only where the class has them).  clip / ema: see FlatOptimizer (None, the default: neither)."""
     if optimizer is None:
-        return FlatAdam(params, lr=lr, betas=tuple(betas))
+        return FlatAdam(params, lr=lr, betas=tuple(betas), clip=clip, ema=ema)
     name = optimizer.get("name", "Adam")
     args = dict(optimizer.get("args") or {})
     args.setdefault("lr", lr)
     if name in ("Adam", "AdamW"):
         args.setdefault("betas", tuple(betas))
-    return FlatOptimizer(params, name, **args)
+    return FlatOptimizer(params, name, clip=clip, ema=ema, **args)
 
 
 class FlatAdam(FlatOptimizer):
     """torch.optim.Adam(params, lr, betas, eps) over one flat parameter buffer: FlatOptimizer with the defaults of the
     shipped configs (no weight decay, no AMSGrad)."""
 
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
-        super().__init__(params, "Adam", lr=lr, betas=betas, eps=eps, amsgrad=False)
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, clip=None, ema=None):
+        super().__init__(params, "Adam", clip=clip, ema=ema, lr=lr, betas=betas, eps=eps, amsgrad=False)

@@ -85,11 +85,16 @@ def synthetic_validation_batch(B, H, W, TB=16, num_frames=4, device="cuda", seed
 class Engine(graphstep.GraphStepper):
     def __init__(self, model_args=None, device="cuda", precision="fp32", lr=1e-4, seed=None, train=True, graph=False,
                  accu_step=1, betas=(0.9, 0.999), backward_f16=None, forward_f16="filters", strict_graph=None,
-                 perceptual=None, optimizer=None, defer_wgrad=True, defer_wgrad_cap=None):
+                 perceptual=None, optimizer=None, defer_wgrad=True, defer_wgrad_cap=None, clip_grad=None, ema=None):
         """graph / accu_step / strict_graph: see graphstep.GraphStepper (a graph is captured per input shape, precision and loss
         phase).
         optimizer: None = Adam with `lr` / `betas` (the shipped config), or the config's optimizer section {"name": "Adam" |
         "AdamW" | "SGD", "args": {...}} (ebfi_amd.dp.FlatOptimizer); `lr` / `betas` fill in what its args leave out.
+        clip_grad: None, or (max_norm, norm_type) with norm_type 2 or inf: the gradient of every optimiser step -- after the
+        accumulation window and the all-reduce -- is clipped by its total norm inside the update's launch (two small launches
+        compute the norm; `optimizer.last_grad_norm` holds norm and coefficient on the device; `param.grad` stays unclipped).
+        ema: None, or (decay, warmup): an exponential moving average of the weights kept by the update's launch; `ema_weights()`
+        puts it under the model, `validate` scores it by default.  With both None not one launch of the step changes.
         perceptual: None, or an ebfi_amd.loss.PerceptualTerm: its value for (Sharp, target), / accu_step, is added to the training
         loss before the backward pass, inside the captured step.  The LPIPS weights are not model parameters: they are neither
         trained nor saved.  With None not one launch of the step changes.
@@ -112,6 +117,8 @@ class Engine(graphstep.GraphStepper):
         early flush (None: wgradqueue.BYTE_CAP)."""
         if precision not in ("fp32", "bf16x3", "bf16"):
             raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
+        if not train and (clip_grad is not None or ema is not None):
+            raise ValueError("clip_grad / ema belong to the optimiser step: they need train=True")
         super().__init__(device, graph=graph, accu_step=accu_step, strict_graph=strict_graph)
         self.precision = precision
         if seed is not None:
@@ -137,7 +144,7 @@ class Engine(graphstep.GraphStepper):
             # one flat parameter buffer (parameters become views of it) updated by ONE fused Adam launch on the packed
             # gradient (0.4 ms per step less than the multi-tensor pass over 255 tensors); state_dict() keeps torch's
             # per-parameter layout for checkpoints
-            self.optimizer = build_flat_optimizer(self.bucket.params, optimizer, lr, betas)
+            self.optimizer = build_flat_optimizer(self.bucket.params, optimizer, lr, betas, clip=clip_grad, ema=ema)
         else:
             self.model.eval()
         # MFMA operand images of every conv weight, refreshed by one launch per step instead of one per conv call
@@ -236,7 +243,7 @@ class Engine(graphstep.GraphStepper):
         return cache[group]
 
     @torch.no_grad()
-    def validate(self, batch, load=0, group=None, refresh=True, eps=1e-3):
+    def validate(self, batch, load=0, group=None, refresh=True, eps=1e-3, use_ema=None):
         """One (batch, load) of the reference's validation loop (train_ours.py:566-591) -> {"valid_loss", "valid_psnr",
         "valid_ssim"}: 0-dim float64 DEVICE tensors.
           valid_loss  sum_i CharbonnierLoss(Final_i, LatentF_i) / NumI, the loss a SUM over the whole batch -- the reference's
@@ -249,10 +256,10 @@ class Engine(graphstep.GraphStepper):
         refresh: re-pack the validator's weight images from the current parameters first (and retake its captured graph).  The native Adam step writes the
         flat parameter buffer through a raw pointer, which moves no tensor version counter, so the validator's bank cannot see
         an optimiser step by itself: pass True (the default) at least for the first batch of every validation pass.
+        use_ema: score the exponential moving average of the weights (`ema_weights()`); None = yes when the engine keeps one.  A
+        caller that scores many batches enters `ema_weights()` once around them: the call then changes nothing.
         Nothing is read back to the host here; the training state (module modes, compute dtype, active bank / book, scale
         book, graphs, gradients, accumulation window) is left as found."""
-        from .loss import charbonnier_per_sample
-        from .metrics import frame_metrics
         if isinstance(batch, dict):
             latent = batch["SeqLatentF"][:, load]
             latent = latent.reshape((latent.shape[0], -1) + tuple(latent.shape[-3:]))        # [B, NumP * NumF, 3, H, W]
@@ -266,6 +273,12 @@ class Engine(graphstep.GraphStepper):
         B, num_i = int(ts.shape[0]), int(ts.shape[-1])
         if latent.dim() != 5 or latent.shape[0] != B or latent.shape[1] != num_i:
             raise ValueError("validate: LatentF %s does not match Ts %s" % (tuple(latent.shape), tuple(ts.shape)))
+        with self._use_ema(use_ema):
+            return self._validate(frame, event, ts, gtex, latent, B, num_i, group, refresh, eps)
+
+    def _validate(self, frame, event, ts, gtex, latent, B, num_i, group, refresh, eps):
+        from .loss import charbonnier_per_sample
+        from .metrics import frame_metrics
         interp = self.validator(group)
         if refresh:
             interp.refresh_weights()

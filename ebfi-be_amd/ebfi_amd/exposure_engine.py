@@ -77,11 +77,12 @@ class ExposureEngine(GraphStepper):
     VALID_KEYS = ("valid_loss", "valid_mae")
 
     def __init__(self, model_args=None, fashion="RGBLap", device="cuda", precision="fp32", lr=1e-4, seed=None, graph=False,
-                 accu_step=1, betas=(0.9, 0.999), strict_graph=None, name="ExposureDecision", optimizer=None):
+                 accu_step=1, betas=(0.9, 0.999), strict_graph=None, name="ExposureDecision", optimizer=None, clip_grad=None,
+                 ema=None):
         """precision: 'fp32' (exact) or 'bf16x3' (split-precision matrix-core operands, fp32-grade accuracy) for the 3x3
         convolutions; the fp16-operand backward of the main engine is not used here.  graph / accu_step / strict_graph: see
         graphstep.GraphStepper.  optimizer: None = Adam with `lr` / `betas`, or the config's optimizer section {"name", "args"}
-        (see Engine)."""
+        (see Engine).  clip_grad / ema: gradient clipping by total norm and the moving average of the weights, as in Engine."""
         check_model_name(name)
         if precision not in ("fp32", "bf16x3"):
             raise ValueError("precision must be 'fp32' or 'bf16x3'")
@@ -101,7 +102,7 @@ class ExposureEngine(GraphStepper):
         self.last_Ex = None
         self.loss = DutyMSELoss(1.0 / self.accu_step)
         self.bucket = FlatGradBucket(self.model)
-        self.optimizer = build_flat_optimizer(self.bucket.params, optimizer, lr, betas)
+        self.optimizer = build_flat_optimizer(self.bucket.params, optimizer, lr, betas, clip=clip_grad, ema=ema)
         self.bank = None
         if self.device.type == "cuda" and precision == "bf16x3":
             from . import weightbank
@@ -132,7 +133,7 @@ class ExposureEngine(GraphStepper):
             return self.model(*self.inputs(frame, event))
 
     @torch.no_grad()
-    def validate(self, batch, load=0, refresh=True):
+    def validate(self, batch, load=0, refresh=True, use_ema=None):
         """One (batch, load) of the reference's _valid (train_ours_exposuredecision.py:546-567) -> {"valid_loss", "valid_mae"}:
         0-dim float64 DEVICE tensors.
           valid_loss  sum over the load's periods of MSELoss(Ex, ExposureDuty) -- the reference's value
@@ -140,6 +141,7 @@ class ExposureEngine(GraphStepper):
         batch: a collated ebfi_amd.clipdata batch (dict, [B, L, ...]; `load` picks the load) or the tuple (Frame [B,NumP,3,H,W] or
         [B,3,H,W], Event [B,TB,2,H,W], Duty [B,NumP,1] or [B,1]).  refresh: accepted for the call contract of Engine.validate
         (the weight images are re-packed from the current parameters on every call here: one launch).
+        use_ema: score the moving average of the weights (`ema_weights()`); None = yes when the engine keeps one.
         Runs in eval mode; module modes, compute dtype, gradients, accumulation window and captured graphs are left as found."""
         if isinstance(batch, dict):
             frames = batch["SeqBlurryF"][:, load]
@@ -155,7 +157,7 @@ class ExposureEngine(GraphStepper):
         try:
             loss = torch.zeros((), dtype=torch.float64, device=frames.device)
             mae = torch.zeros((), dtype=torch.float64, device=frames.device)
-            with self._autocast(), self._bank():
+            with self._use_ema(use_ema), self._autocast(), self._bank():
                 for i in range(num_p):
                     duty = duties[:, i].reshape(-1, 1).float()
                     # (Ex through the native head's loss-free form: two launches instead of the pooling / sigmoid tail)

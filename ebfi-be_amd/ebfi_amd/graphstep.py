@@ -109,6 +109,78 @@ class GraphStepper:
         self.bank.refresh()
         return self.bank.active()
 
+    # ------------------------------------------------------------------------------------------------ averaged weights
+    @property
+    def has_ema(self):
+        opt = getattr(self, "optimizer", None)
+        return opt is not None and getattr(opt, "ema", None) is not None
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside: the model computes with the exponential moving average of the weights (FlatOptimizer(ema=...)).  The CONTENTS
+        of the flat parameter buffer and of the average are exchanged -- parameters are views of that buffer, so the model, a
+        checkpoint written inside and the validator all see the averaged weights -- and exchanged back on exit, bit for bit.
+        Buffers that are not parameters (running statistics of norm layers) are shared.  No tensor moves, so the captured
+        graphs, the training bank (re-packed from the flat buffer by every training pass), the scale book and the accumulation
+        window are left as found.  Nesting is allowed: an inner context changes nothing.  Not for use around `train_step`."""
+        if not self.has_ema:
+            raise ValueError("this engine keeps no moving average of the weights: build it with ema=(decay, warmup)")
+        if getattr(self, "_ema_inside", False):
+            yield self
+            return
+        self.optimizer.swap_ema()
+        self._ema_inside = True
+        try:
+            yield self
+        finally:
+            self._ema_inside = False
+            self.optimizer.swap_ema()
+
+    def _use_ema(self, use_ema):
+        """`use_ema` of a validate call -> the context to score under: None = the average when there is one."""
+        if use_ema is None:
+            use_ema = self.has_ema
+        return self.ema_weights() if use_ema else contextlib.nullcontext()
+
+    def _trainable_names(self):
+        return [n for n, p in self.model.named_parameters() if p.requires_grad]
+
+    def ema_state(self):
+        """The `ema` entry of a checkpoint: {"decay", "warmup", "step", "states"}; `states` has the state_dict layout of the
+        model's trainable parameters (name -> tensor, a copy) and holds the AVERAGE whether or not the call happens inside
+        `ema_weights()`.  None without an average.  Reads the device's step word: a checkpoint may synchronise."""
+        if not self.has_ema:
+            return None
+        opt = self.optimizer
+        decay, warmup = opt.ema
+        if getattr(self, "_ema_inside", False):                       # (the buffers hold each other's contents in there)
+            views = [p.detach() for p in opt.params]
+        else:
+            views = opt.ema_views()
+        return {"decay": decay, "warmup": warmup, "step": int(float(opt.ema_step)),
+                "states": {n: v.clone() for n, v in zip(self._trainable_names(), views)}}
+
+    @torch.no_grad()
+    def load_ema_state(self, state=None):
+        """Restore the average from a checkpoint's `ema` entry; None (a checkpoint without one, or --reset): start it from the
+        current parameters.  decay and warm-up stay this run's.  A name or shape that does not match raises."""
+        if not self.has_ema:
+            return
+        opt = self.optimizer
+        if state is None:
+            opt.reset_ema()
+            return
+        names, views = self._trainable_names(), opt.ema_views()
+        missing = [n for n in names if n not in state["states"]]
+        if missing:
+            raise ValueError("checkpoint ema.states lacks %d of the model's trainable parameters (first: %s)" % (len(missing), missing[0]))
+        for n, v in zip(names, views):
+            src = state["states"][n]
+            if tuple(src.shape) != tuple(v.shape):
+                raise ValueError("checkpoint ema.states[%s] has shape %r, the model %r" % (n, tuple(src.shape), tuple(v.shape)))
+            v.copy_(src.to(v))
+        opt.ema_step.fill_(float(state.get("step", 0)))
+
     # ------------------------------------------------------------------------------------------------ the step
     def _finish_micro_step(self, wire):
         """`wire`: this call's packed gradient (of loss / accu_step) with the overflow flag behind it (FlatGradBucket.wire).

@@ -4,7 +4,9 @@ per-layer weight / gradient statistics, for both trainers (train_loop of train_o
 Scalars   `train_loss/train` and `learning rate` for every iteration, `steps_per_sec/train` as the average of each flushed interval.
           No host read per iteration: after a step the loss tensor is copied device-to-device into a ring; at each train_log_step,
           at a validation stamp or when the ring is full ONE mean all-reduce and ONE download flush it.  `valid_loss/valid` per
-          validation (batch, load), `stamp_<key>` per validation stamp and `stamp_train_loss`.
+          validation (batch, load), `stamp_<key>` per validation stamp and `stamp_train_loss`.  With gradient clipping on
+          (trainer.clip_grad) `grad_norm/total` and `grad_norm/clip_coef` for every iteration: the two floats the norm launches
+          leave on the device travel through a second ring that is downloaded with the first.
 Images    (trainer.vis.enabled) every train_img_writer_num-th iteration / valid_img_writer_num-th validation batch, sample 0:
           `<side>_HR_events` = event_count_images(Event.sum(1)[:1], 'green_red', black_background=True) and `<side>_blurry_frame`,
           `<side>_sharp_frame`, `<side>_gt_frame` through ONE planar_to_u8 call; the four pictures come back in one download that
@@ -133,6 +135,9 @@ class TrainMonitor:
         self.stats_factory = stats_factory or telemetry.SegmentStats
         self.ring_size = max(1, int(ring))
         self._ring, self._meta = None, []              # device ring of losses; host (iteration, lr) per slot
+        # second ring, only with gradient clipping on: [total norm, clipping coefficient] of every step, copied on the device from
+        # FlatOptimizer.last_grad_norm and downloaded with the loss ring (the same bits on every rank: no collective)
+        self._norm_ring, self.last_grad_norm = None, None
         self._mark = time.perf_counter()               # start of the interval steps_per_sec averages over
         self.last_train_loss = float("nan")
         self._jobs = _WriterThread() if self.writer is not None else None
@@ -164,6 +169,11 @@ class TrainMonitor:
         if self._ring is None:
             self._ring = torch.zeros(self.ring_size, dtype=torch.float32, device=loss.device)
         self._ring[len(self._meta)].copy_(loss.detach().reshape(()))
+        norm = getattr(getattr(eng, "optimizer", None), "last_grad_norm", None)
+        if norm is not None:
+            if self._norm_ring is None:
+                self._norm_ring = torch.zeros(self.ring_size, 2, dtype=torch.float32, device=norm.device)
+            self._norm_ring[len(self._meta)].copy_(norm)
         self._meta.append((int(it), float(lr)))
         if self.rank == 0:
             if self.s["vis_enabled"] and it % self.s["train_img_writer_num"] == 0 and eng is not None and batch is not None:
@@ -182,6 +192,8 @@ class TrainMonitor:
         if k == 0:
             return self.last_train_loss
         host = reduce_tensor(self._ring[:k].clone()).cpu().numpy()
+        # (a copy in every case: on host tensors .cpu() is the ring itself, which later steps overwrite before the writer runs)
+        norms = None if self._norm_ring is None else self._norm_ring[:k].to("cpu", copy=True).numpy()
         now = time.perf_counter()
         if self.writer is not None:
             meta, rate = self._meta, k / max(now - self._mark, 1e-9)
@@ -190,11 +202,17 @@ class TrainMonitor:
                 for (it, lr), v in zip(meta, host):
                     self.writer.add_scalar("train_loss/train", v, it)
                     self.writer.add_scalar("learning rate", lr, it)
+                if norms is not None:
+                    for (it, _), (total, coef) in zip(meta, norms):
+                        self.writer.add_scalar("grad_norm/total", total, it)
+                        self.writer.add_scalar("grad_norm/clip_coef", coef, it)
                 self.writer.add_scalar("steps_per_sec/train", rate, meta[-1][0])
                 self.writer.flush()
             self._jobs.submit(None, write)
         self._mark = now
         self.last_train_loss = float(host[-1])
+        if norms is not None:
+            self.last_grad_norm = (float(norms[-1][0]), float(norms[-1][1]))
         self._meta = []
         return self.last_train_loss
 

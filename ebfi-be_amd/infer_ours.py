@@ -83,16 +83,30 @@ def warn(msg):
     print("infer_ours.py: " + msg, file=sys.stderr, flush=True)
 
 
-def load_model(model_path, device):
+def load_model(model_path, device, ema=False):
+    """ema: load the checkpoint's exponential moving average of the weights (its `ema.states`, written by a training run with
+    trainer.ema / --ema-decay) over the model: trainable parameters from the average, everything else from model.states."""
+    averaged = None
     if model_path is None:
+        if ema:
+            raise SystemExit("infer_ours.py: --ema needs a checkpoint (--model_path)")
         name, margs, states = "EVFIAutoEx", dict(DEFAULT_MODEL_ARGS), None
     else:
         assert os.path.isfile(model_path), model_path
         cpt = torch.load(model_path, map_location="cpu", weights_only=False)
         name, margs, states = cpt["config"]["model"]["name"], cpt["config"]["model"]["args"], cpt["model"]["states"]
+        if ema:
+            if not isinstance(cpt.get("ema"), dict) or not cpt["ema"].get("states"):
+                raise SystemExit("infer_ours.py: --ema: %s holds no averaged weights (no `ema` entry: it was written by a run "
+                                 "without trainer.ema / --ema-decay)" % model_path)
+            averaged = cpt["ema"]["states"]
     model = globals()[name](**margs)
     if states is not None:
         model.load_state_dict(states)
+    if averaged is not None:
+        unknown = model.load_state_dict(averaged, strict=False).unexpected_keys
+        if unknown:
+            raise SystemExit("infer_ours.py: --ema: ema.states names parameters the model does not have (first: %s)" % unknown[0])
     return model.to(device).eval(), margs
 
 
@@ -121,6 +135,9 @@ def get_flags(argv=None):
                     help="as in the reference this flag SWITCHES THE EVENT NOISE OFF (store_false; 'false for real-world data')")
     ap.add_argument("--center_crop_size", type=int, nargs="+", default=None)
     ap.add_argument("--real_blur", default=False, action="store_true")
+    ap.add_argument("--ema", action="store_true",
+                    help="run the checkpoint's exponential moving average of the weights (its `ema` entry) instead of the raw "
+                         "iterate; ends with a message when the checkpoint holds none")
     # ---- this implementation's own ----
     ap.add_argument("--png", action="store_true", help="also write the reference's PNG tree (needs PIL)")
     ap.add_argument("--event_png", action="store_true",
@@ -516,7 +533,7 @@ def main(argv=None):
     if device.type != "cuda":
         raise SystemExit("infer_ours.py: the MI355X path needs a cuda device (got --device %s); there is no CPU fallback" % a.device)
     torch.cuda.set_device(device)
-    model, margs = load_model(a.model_path, device)
+    model, margs = load_model(a.model_path, device, ema=a.ema)
     if a.rand_init and a.model_path is None:
         with torch.no_grad():
             for p in model.parameters():

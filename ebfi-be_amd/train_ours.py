@@ -24,11 +24,19 @@ images with trainer.vis.enabled; per-layer weight / gradient statistics with tra
 The reference's perceptual_loss(net='vgg') (train_ours.py:765) is an optional term: `--lpips_weight W` (or trainer.lpips_weight)
 with `--lpips_lin` / `--lpips_backbone` adds W x LPIPS(Sharp, target), mean over the batch, to the loss above, differentiated by
 ebfi_amd.lpips on the device inside the (captured) step; the log line then names the term.  Off (W = 0) by default.
+Two things the reference trains without, both off by default: `trainer.clip_grad: {max_norm, norm_type}` / `--clip-grad-norm X` clips
+every optimiser step's gradient by its total norm (norm_type 2 or inf) inside the update's launch -- the log line then shows
+grad_norm, the TensorBoard log `grad_norm/total` and `grad_norm/clip_coef` -- and `trainer.ema: {decay, warmup, validate}` /
+`--ema-decay D` keeps an exponential moving average of the weights that validation, the monitor and the best checkpoint score
+(validate: false keeps them on the raw iterate) and checkpoints carry as a sixth key, `ema: {decay, warmup, step, states}`, next to
+an unchanged `model.states`; --resume restores it, --reset or a checkpoint without it starts it from the loaded weights, and
+`infer_ours.py --ema` runs it.
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train_ours.py -c config/train_ours.yml -id run
     python train_ours.py -c config/train_ours.yml -id run --iterations 20
 """
 import argparse
+import contextlib
 import math
 import os
 import sys
@@ -125,6 +133,41 @@ def perceptual_settings(config, args):
     return weight, args.lpips_lin, args.lpips_backbone
 
 
+def averaging_settings(config, args=None):
+    """{"clip_grad": (max_norm, norm_type) | None, "ema": (decay, warmup) | None, "ema_validate": bool} from trainer.clip_grad
+    {max_norm, norm_type = 2} and trainer.ema {decay, warmup = false, validate = true}; --clip-grad-norm X and --ema-decay D
+    override max_norm and decay (and switch the feature on where the config is silent).  Absent: off.  max_norm <= 0, a
+    norm_type other than 2 / inf, a decay outside [0, 1) or an unknown key raise ValueError here, before any device work."""
+    from ebfi_amd.dp import clip_arguments, ema_arguments
+    tr = config.get("trainer", {}) or {}
+    clip, ema = tr.get("clip_grad"), tr.get("ema")
+    clip = dict(clip) if isinstance(clip, dict) else (None if clip is None else {"max_norm": clip})
+    ema = dict(ema) if isinstance(ema, dict) else (None if ema is None else {"decay": ema})
+    if getattr(args, "clip_grad_norm", None) is not None:
+        clip = dict(clip or {}, max_norm=args.clip_grad_norm)
+    if getattr(args, "ema_decay", None) is not None:
+        ema = dict(ema or {}, decay=args.ema_decay)
+    validate = True
+    if ema is not None:
+        unknown = set(ema) - {"decay", "warmup", "validate"}
+        if unknown:
+            raise ValueError("trainer.ema takes decay, warmup and validate, got %r" % (sorted(ema),))
+        validate = bool(ema.pop("validate", True))
+    if clip is not None and isinstance(clip.get("norm_type"), str):
+        clip["norm_type"] = float(clip["norm_type"])              # (YAML spells infinity `.inf`; 'inf' is accepted too)
+    return {"clip_grad": clip_arguments(clip), "ema": ema_arguments(ema), "ema_validate": validate}
+
+
+def add_averaging_arguments(ap):
+    """--clip-grad-norm / --ema-decay of both trainers."""
+    ap.add_argument("--clip-grad-norm", dest="clip_grad_norm", type=float, default=None,
+                    help="clip every optimiser step's gradient to this total norm (trainer.clip_grad.max_norm; the norm type comes "
+                         "from trainer.clip_grad.norm_type, 2 by default) inside the update's launch; default: the config's, else off")
+    ap.add_argument("--ema-decay", dest="ema_decay", type=float, default=None,
+                    help="keep an exponential moving average of the weights with this decay (trainer.ema.decay) for validation, "
+                         "best-model tracking, checkpoints (`ema` key) and infer_ours.py --ema; default: the config's, else off")
+
+
 def optimizer_settings(config, args=None):
     """{"name", "args"} of the optimiser from the config's `optimizer` section, the reference's
     eval(config['optimizer']['name'])(trainable_params, **config['optimizer']['args']) (train_ours.py:770-771): Adam, AdamW or
@@ -197,11 +240,13 @@ def checkpoint_state(eng, scheduler, config, iteration, monitor_best=None):
     """The reference's checkpoint dict (train_ours.py:628-655), key for key; `iteration` = index of the last completed
     optimiser step, resumed at +1 (:695)."""
     sched_name = (config.get("lr_scheduler") or {}).get("name")
-    return {"model": {"name": config["model"]["name"], "states": eng.model.state_dict()},
+    ema = eng.ema_state() if getattr(eng, "has_ema", False) else None
+    extra = {} if ema is None else {"ema": ema}       # (a sixth key only when the run keeps an average: model.states stays raw)
+    return dict({"model": {"name": config["model"]["name"], "states": eng.model.state_dict()},
             "lr_scheduler": {"name": sched_name, "states": scheduler.state_dict() if scheduler is not None else {}},
             "optimizer": {"name": config["optimizer"]["name"], "states": eng.optimizer.state_dict()},
             "config": config,
-            "trainer": {"training_mode": TRAINING_MODE, "iteration": int(iteration), "monitor_best": monitor_best}}
+            "trainer": {"training_mode": TRAINING_MODE, "iteration": int(iteration), "monitor_best": monitor_best}}, **extra)
 
 
 def save_checkpoint(path, eng, scheduler, config, iteration, monitor_best=None, save_best=False):
@@ -220,10 +265,12 @@ def resume_checkpoint(path, eng, scheduler, config, reset=False, map_location="c
     scheduler states are restored only without --reset and when the training mode matches, each only when the configured
     name equals the checkpoint's; the model is always loaded (strict=False) when its name matches.  monitor: a Monitor whose
     `best` is restored from trainer.monitor_best under the same condition as the optimiser state (:696; a checkpoint written
-    without validation carries None and leaves it alone); its not_improved_count restarts at 0.  Returns the first iteration
-    to run."""
+    without validation carries None and leaves it alone); its not_improved_count restarts at 0.  An engine that keeps a moving
+    average of the weights takes it from the checkpoint's `ema` entry under that condition too; with --reset, another training
+    mode or a checkpoint without the entry the average starts from the loaded weights.  Returns the first iteration to run."""
     cpt = torch.load(path, map_location=map_location, weights_only=False)
     start = 0
+    ema = None
     tr = cpt["trainer"]
     if not reset and tr.get("training_mode") == TRAINING_MODE:
         if config["optimizer"]["name"] == cpt["optimizer"]["name"]:
@@ -233,10 +280,13 @@ def resume_checkpoint(path, eng, scheduler, config, reset=False, map_location="c
             for group, lr in zip(eng.optimizer.param_groups, scheduler.get_last_lr()):
                 group["lr"] = lr
         start = int(tr["iteration"]) + 1
+        ema = cpt.get("ema")
         if monitor is not None and monitor.mode != "off" and tr.get("monitor_best") is not None:
             monitor.best = tr["monitor_best"]
     if config["model"]["name"] == cpt["model"]["name"]:
         eng.model.load_state_dict(cpt["model"]["states"], strict=False)
+    if getattr(eng, "has_ema", False):
+        eng.load_ema_state(ema if config["model"]["name"] == cpt["model"]["name"] else None)
     eng.iteration = start
     return start
 
@@ -340,23 +390,29 @@ def validation_batches(vs, config, args, B, H, W, TB, device, rank, world):
     return lambda: iter(mine)
 
 
-def run_validation(eng, batches, tracker, stamp, log_step=50, rank=0, telemetry=None):
+def run_validation(eng, batches, tracker, stamp, log_step=50, rank=0, telemetry=None, use_ema=None):
     """_valid of the reference (train_ours.py:545-619) for one stamp: every (batch, load) is scored by Engine.validate, averaged
     over ranks (reduce_tensor: ONE collective and ONE host read per (batch, load), none per timestamp) and averaged over the
     stamp by the MetricTracker.  Every rank feeds its tracker with the same reduced values.  Returns tracker.result().
-    telemetry: an ebfi_amd.monitor.TrainMonitor that logs every (batch, load), or None."""
+    telemetry: an ebfi_amd.monitor.TrainMonitor that logs every (batch, load), or None.
+    use_ema (an engine that keeps a moving average of the weights; trainer.ema.validate): None / True score the average -- the
+    whole stamp runs inside ONE eng.ema_weights() -- False the raw iterate."""
     tracker.reset()
-    for k, batch in enumerate(batches()):
-        loads = batch["SeqLatentF"].shape[1] if isinstance(batch, dict) else 1
-        for load in range(loads):
-            vals = eng.validate(batch, load=load, refresh=(k == 0 and load == 0))      # weights re-packed once per pass
-            host = reduce_tensor(torch.stack([vals[key] for key in eng.VALID_KEYS])).tolist()
-            for key, v in zip(eng.VALID_KEYS, host):
-                tracker.update(key, v)
-            if telemetry is not None:
-                telemetry.valid_batch(host[0], eng)
-            if rank == 0 and k % log_step == 0:
-                print("Valid timestamp: %d [batch %d] valid_loss: %.4e" % (stamp, k, host[0]), flush=True)
+    has_ema = bool(getattr(eng, "has_ema", False))
+    averaged = has_ema and (use_ema is None or bool(use_ema))
+    kw = {"use_ema": False} if has_ema and not averaged else {}
+    with (eng.ema_weights() if averaged else contextlib.nullcontext()):
+        for k, batch in enumerate(batches()):
+            loads = batch["SeqLatentF"].shape[1] if isinstance(batch, dict) else 1
+            for load in range(loads):
+                vals = eng.validate(batch, load=load, refresh=(k == 0 and load == 0), **kw)      # weights re-packed once per pass
+                host = reduce_tensor(torch.stack([vals[key] for key in eng.VALID_KEYS])).tolist()
+                for key, v in zip(eng.VALID_KEYS, host):
+                    tracker.update(key, v)
+                if telemetry is not None:
+                    telemetry.valid_batch(host[0], eng)
+                if rank == 0 and k % log_step == 0:
+                    print("Valid timestamp: %d [batch %d] valid_loss: %.4e" % (stamp, k, host[0]), flush=True)
     return tracker.result()
 
 
@@ -388,8 +444,14 @@ def train_loop(eng, next_micro_batch, samples_per_pass, unit, st, vs, scheduler,
         if rank == 0 and log_now:
             torch.cuda.synchronize()
             rate = samples / (time.perf_counter() - t0) if t0 is not None and samples else float("nan")
-            print("Iteration: %d/%d train_loss: %.4e%s learning rate: %.4e  %.1f %s/s"
-                  % (it, st["iterations"], loss.item(), loss_note, lr_now, rate, unit), flush=True)
+            # with clipping on: the total norm of this iteration's gradient, from the monitor's second ring (its flush just
+            # downloaded it) or, without a monitor, read here -- at the log step only, after the synchronisation above
+            norm_note, norm = "", getattr(getattr(eng, "optimizer", None), "last_grad_norm", None)
+            if norm is not None:
+                shown = telemetry.last_grad_norm[0] if telemetry is not None and telemetry.last_grad_norm else float(norm[0])
+                norm_note = " grad_norm: %.4e" % shown
+            print("Iteration: %d/%d train_loss: %.4e%s%s learning rate: %.4e  %.1f %s/s"
+                  % (it, st["iterations"], loss.item(), loss_note, norm_note, lr_now, rate, unit), flush=True)
         if t0 is None and eng.settled:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -397,7 +459,8 @@ def train_loop(eng, next_micro_batch, samples_per_pass, unit, st, vs, scheduler,
         best = stop = False
         if vs["do_validation"] and it % vs["valid_step"] == 0 and it != 0:
             t_valid = time.perf_counter()
-            val_log = run_validation(eng, valid_batches, tracker, valid_stamp, vs["valid_log_step"], rank, telemetry=telemetry)
+            val_log = run_validation(eng, valid_batches, tracker, valid_stamp, vs["valid_log_step"], rank, telemetry=telemetry,
+                                     use_ema=vs.get("use_ema"))
             if telemetry is not None:
                 telemetry.stamp(valid_stamp, val_log)
                 telemetry.pause(time.perf_counter() - t_valid)
@@ -466,6 +529,7 @@ def get_args(argv=None):
                     help="LPIPS: torchvision's VGG-16 state dict (vgg16-397923af.pth of the torch hub cache)")
     add_loader_arguments(ap)
     add_monitor_arguments(ap)
+    add_averaging_arguments(ap)
     return ap.parse_args(argv)
 
 
@@ -475,9 +539,11 @@ def main(argv=None):
         config = yaml.safe_load(fh)
     lpips_weight, lpips_lin, lpips_backbone = perceptual_settings(config, args)      # (refuses before any device work)
     optimizer = optimizer_settings(config, args)                                      # (likewise)
+    averaging = averaging_settings(config, args)                                      # (likewise)
     tr = config.get("trainer", {}) or {}
     st = trainer_settings(config, args.iterations)
     vs = validation_settings(config, args.valid_data)
+    vs["use_ema"] = averaging["ema_validate"]
     rank, world, gpu = init_distributed_mode()
     device = torch.device("cuda", gpu)
     assert config["model"]["name"] == "EVFIAutoEx", "only the EVFIAutoEx hot path is implemented"
@@ -492,7 +558,7 @@ def main(argv=None):
                  seed=args.seed,                                                      # same init on every rank
                  graph=args.graph or bool(tr.get("graph", False)), accu_step=st["accu_step"],
                  backward_f16=False if args.no_f16_backward else None, forward_f16=None if args.no_f16_forward else "filters",
-                 perceptual=perceptual)
+                 perceptual=perceptual, clip_grad=averaging["clip_grad"], ema=averaging["ema"])
     scheduler = build_lr_scheduler(config, eng.optimizer.inner)
     # monitor / best checkpoint / early stop (train_ours.py:155-163): only with validation on -- otherwise monitor_best stays None
     monitor = Monitor(vs["monitor"], vs["early_stop"],

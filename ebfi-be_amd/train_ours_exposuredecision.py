@@ -28,7 +28,8 @@ import yaml
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
-from train_ours import (CHECKPOINT_KEYS, TRAINING_MODE, Monitor, add_loader_arguments, add_monitor_arguments,  # noqa: E402,F401
+from train_ours import (CHECKPOINT_KEYS, TRAINING_MODE, Monitor, add_averaging_arguments, add_loader_arguments,  # noqa: E402,F401
+                        add_monitor_arguments, averaging_settings,
                         best_checkpoint_name, build_lr_scheduler, build_monitor, checkpoint_state, clip_dataset, init_distributed_mode,
                         optimizer_settings, resume_checkpoint, save_checkpoint, train_loop, trainer_settings, validation_seeds, validation_settings, with_noise_law)
 from ebfi_amd.exposure_engine import (BLURRY_FASHIONS, check_fashion, check_model_name,  # noqa: E402,F401
@@ -65,6 +66,7 @@ def build_parser():
                          "either: a fixed set of trainer.valid_batches synthetic batches)")
     add_loader_arguments(ap)
     add_monitor_arguments(ap)
+    add_averaging_arguments(ap)
     return ap
 
 
@@ -133,6 +135,8 @@ def main(argv=None):
     if args.batch_size:
         es["batch_size"] = int(args.batch_size)
     optimizer = optimizer_settings(config, args)      # (-lr overrides optimizer.args.lr; refuses before any device work)
+    averaging = averaging_settings(config, args)      # (trainer.clip_grad / trainer.ema, --clip-grad-norm / --ema-decay; likewise)
+    vs["use_ema"] = averaging["ema_validate"]
     rank, world, gpu = init_distributed_mode()
     device = torch.device("cuda", gpu)
     from ebfi_amd.exposure_engine import ExposureEngine
@@ -140,7 +144,8 @@ def main(argv=None):
 
     eng = ExposureEngine(es["model_args"], fashion=es["fashion"], device=device, precision=args.precision,
                          optimizer=optimizer, seed=args.seed,
-                         graph=args.graph or bool(tr.get("graph", False)), accu_step=st["accu_step"], name=es["name"])
+                         graph=args.graph or bool(tr.get("graph", False)), accu_step=st["accu_step"], name=es["name"],
+                         clip_grad=averaging["clip_grad"], ema=averaging["ema"])
     scheduler = build_lr_scheduler(config, eng.optimizer.inner)
     monitor = Monitor(vs["monitor"], vs["early_stop"],
                       warn=None if rank == 0 else (lambda msg: None)) if vs["do_validation"] else None

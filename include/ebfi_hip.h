@@ -36,6 +36,9 @@
  *   ebfi_laploss_*              whole Laplacian-pyramid L1 term of a step as one difference pyramid (loss/restore.py:166-213)
  *   ebfi_adam_step              optimizer.step() of train_ours.py:276-277 over the flat parameter buffer
  *   ebfi_optim_step             the same for every optimiser the config may name: torch.optim.Adam / AdamW / SGD (train_ours.py:770-771)
+ *   ebfi_grad_norm              the norm and coefficient of torch.nn.utils.clip_grad_norm_ over the flat gradient, left on the device
+ *   ebfi_optim_step_ex          ebfi_optim_step with that coefficient and an exponential moving average of the weights in the same
+ *                               launch (no counterpart in the reference, which trains without either)
  *   ebfi_grad_gather            gradient bucket packing of DistributedDataParallel (train_ours.py:754) as one launch
  *   ebfi_gather_sum             weight re-layouts of the depth-2 Conv3d / ConvTranspose3d (models/model_misc/resnet_3D.py)
  *   ebfi_events_to_stack        dataloader/encodings.py:307-350 (events_to_stack)
@@ -113,7 +116,8 @@ extern "C" {
  *      ebfi_conv2d_backward_weight_f16g_multi (the pure weight gradients of a training step, deferred and run in one launch) and
  *      ebfi_gather_sum_multi (their fold gathers), likewise; and ebfi_event_augment / ebfi_event_hot_pixels (the device noise
  *      law of the clip loaders), likewise; and ebfi_dcn_pooling_forward / _backward (the deformable PS-ROI pooling of the
- *      DCNv2 package), likewise */
+ *      DCNv2 package), likewise; and ebfi_grad_norm_workspace / ebfi_grad_norm / ebfi_optim_step_ex (gradient clipping by
+ *      total norm and an exponential moving average of the weights around the optimiser step), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -748,6 +752,52 @@ int ebfi_adam_step_guarded(float *param, const float *grad, float *exp_avg, floa
 int ebfi_optim_step(int kind, int flags, float *param, const float *grad, float *state0, float *state1, float *state2,
                     float *step, int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
                     double momentum, double dampening, int *guard, const float *flag, void *stream);
+
+/* Total norm of the flat gradient and the clipping coefficient of torch.nn.utils.clip_grad_norm_, both left ON THE DEVICE
+ * (no host synchronisation): grad float32 [n], 16-byte aligned, only read; out float32 [2].
+ *   out[0] = (float)sqrt(sum g^2) (EBFI_NORM_L2) or max |g| (EBFI_NORM_INF)
+ *   out[1] = c = (float)max_norm / (out[0] + 1e-6f), then c > 1 ? 1 : c -- float32, nothing contracted: torch's arithmetic,
+ *            also for a non-finite norm (NaN norm -> NaN coefficient, infinite norm -> 0)
+ * Two launches.  The first gives every workgroup one chunk of EBFI_GRAD_NORM_CHUNK elements (16-byte loads; the n % 4 last
+ * elements by scalar loads in the workgroup that owns them): every value is widened to float64, squares and sums are float64
+ * (a float32 sum of squares overflows at |g| ~ 1.8e19 and flushes squares below 1e-38), folded per thread in index order and
+ * then by a fixed tree over the workgroup into ONE float64 partial in the workspace.  The second is one workgroup that folds
+ * the partials the same way (thread t takes partials t, t + 256, ... in index order, then the same tree) and writes `out`.
+ * No floating-point atomics, no completion counters: the work split depends on n only and two calls on the same data give the
+ * same bits.  NaN and Inf reach out[0]: a NaN anywhere makes it NaN (the max keeps a NaN on either side, as torch.maximum),
+ * +-Inf makes it +Inf.  n == 0: one launch, out = {0, 1}; the workspace may be NULL then.
+ * workspace: ebfi_grad_norm_workspace(n) bytes = 8 ceil(n / EBFI_GRAD_NORM_CHUNK) (host arithmetic; 0 for n <= 0), 16-byte
+ * aligned, overwritten by every call.  No allocation, no synchronisation: capturable.
+ * Null grad (n > 0) / out, n < 0, an unknown norm_kind, max_norm not positive (or NaN), misaligned grad or workspace ->
+ * EBFI_ERR_ARG; a missing or short workspace -> EBFI_ERR_WORKSPACE; a grid beyond 2^31 - 1 -> EBFI_ERR_UNSUPPORTED; none of them
+ * touches the GPU. */
+#define EBFI_NORM_L2 0
+#define EBFI_NORM_INF 1
+#define EBFI_GRAD_NORM_CHUNK 16384
+int64_t ebfi_grad_norm_workspace(int64_t n);
+int ebfi_grad_norm(const float *grad, int64_t n, int norm_kind, double max_norm, float *out, void *workspace,
+                   int64_t workspace_bytes, void *stream);
+
+/* ebfi_optim_step with a gradient scale and an exponential moving average of the parameters folded into the SAME launch.
+ * Arguments up to `flag` as in ebfi_optim_step.  With grad_scale == NULL and ema == NULL the call IS ebfi_optim_step (forwarded
+ * unchanged: the same kernels, the same bits).  Otherwise ONE launch of the spelled-out law of ebfi_optim_step's variants,
+ * operation by operation, contraction off -- plain Adam (no weight decay, no AMSGrad) included, which here runs that law
+ * instead of the kernel of ebfi_adam_step:
+ *   g' = g * grad_scale[0]          first: before the L2 weight-decay fma, as clipping precedes the optimiser in torch.
+ *                                   grad_scale: one device float (out + 1 of ebfi_grad_norm), NULL = no scale.  `grad` is only
+ *                                   read, the scaled gradient is never written anywhere.
+ *   the update of ebfi_optim_step on g' -> p_new
+ *   e <- e + w (p_new - e)          ema float32 [n], 16-byte aligned, NULL = none; w = (float)(1 - d) with d = ema_decay, or
+ *                                   min(ema_decay, (1 + t) / (10 + t)) when ema_warmup != 0; t = ema_step[0] in double.
+ * ema_step: one device float holding the ALREADY incremented count of applied averages (the host increments it before the
+ * launch), required with ema.  guard / flag: the protocol of ebfi_optim_step, extended: a skipped step writes no parameter, no
+ * state and no ema element, takes BOTH step words back and counts ONCE in guard[1].
+ * Errors as ebfi_optim_step; ema without ema_step, a misaligned ema, ema_decay outside [0, 1) -> EBFI_ERR_ARG.
+ * Bytes moved per launch: those of ebfi_optim_step + 8 n with ema. */
+int ebfi_optim_step_ex(int kind, int flags, float *param, const float *grad, float *state0, float *state1, float *state2,
+                       float *step, int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                       double momentum, double dampening, int *guard, const float *flag, const float *grad_scale, float *ema,
+                       float *ema_step, double ema_decay, int ema_warmup, void *stream);
 
 /* Gradient packing of a training step (replaces the bucket copy of DistributedDataParallel, train_ours.py:754, and the
  * 255-piece concatenation of earlier rounds): `grads` / `numels` are HOST arrays of `count` device pointers (NULL: that
