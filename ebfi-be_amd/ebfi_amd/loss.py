@@ -269,8 +269,9 @@ class TrainLoss(nn.Module):
 
 
 class PerceptualTerm:
-    """weight * mean over the batch of LPIPS (VGG-16) as a term of the training loss (the reference builds perceptual_loss beside
-    Lap and census, train_ours.py:765): `model` is an ebfi_amd.lpips.VggLPIPS, whose weights are no parameters of the trained
+    """weight * mean over the batch of LPIPS as a term of the training loss (the reference builds perceptual_loss beside
+    Lap and census, train_ours.py:765, with the AlexNet trunk): `model` is any LPIPS model with `loss` -- an
+    ebfi_amd.lpips.AlexLPIPSLoss, the reference's trunk, or a VggLPIPS -- whose weights are no parameters of the trained
     model and enter no checkpoint.  term(pred, target) -> 0-dim tensor with a graph into pred; images in [0, 1]."""
 
     def __init__(self, model, weight):

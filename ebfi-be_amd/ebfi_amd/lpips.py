@@ -13,11 +13,17 @@ synchronisation -- and returns the float32 device tensor lpips [N].  Definition:
 the library's exact-fp32 3x3 forward and one tap kernel per layer.  ``load_lpips(net, ...)`` dispatches over 'alex' and 'vgg'.
 
 ``VggLPIPS.loss(pred, target)`` is the same value as a training loss (the reference builds perceptual_loss beside its Laplacian
-and census terms, train_ours.py:765): one autograd node whose forward, ``ebfi_lpips_vgg_forward_train``, keeps the 13 ReLU maps of
-the pred images and the 5 tap maps of the target images, and whose backward, ``ebfi_lpips_vgg_backward``, runs one fused tap
-adjoint per layer (distance gradient plus the max-pool's routed gradient) and the 13 data gradients of the library's exact-fp32
-3x3 kernel.  pred gets the gradient, the target none.  The AlexNet trunk is forward-only: its 11x11 stride-4 and 5x5 layers have
-no data-gradient kernel in the library, so ``AlexLPIPS`` has no ``loss``.
+and census terms, train_ours.py:765 -- with its default trunk, AlexNet): one autograd node whose forward,
+``ebfi_lpips_vgg_forward_train``, keeps the 13 ReLU maps of the pred images and the 5 tap maps of the target images, and whose
+backward, ``ebfi_lpips_vgg_backward``, runs one fused tap adjoint per layer (distance gradient plus the max-pool's routed
+gradient) and the 13 data gradients of the library's exact-fp32 3x3 kernel.  pred gets the gradient, the target none.
+
+``AlexLPIPSLoss`` (``load_alex_lpips(..., train=True)``) is the AlexNet trunk with the same ``loss``: the reference's own
+training term.  Its forward, ``ebfi_lpips_alex_forward_train``, is the score's kernels on a workspace that also holds two
+gradient maps; its backward, ``ebfi_lpips_alex_backward``, runs five tap adjoints (the 3x3/s2 pools' gradient gathered inside),
+an exact-fp32 MFMA data gradient for conv5 .. conv2 (3x3 and 5x5) and a direct one for the 11x11 stride-4 layer, whose
+epilogue writes the gradient of pred.  ``AlexLPIPS`` itself stays a score and has no ``loss``: the data-gradient
+weights are packed only for the loss class.
 """
 import weakref
 
@@ -62,8 +68,8 @@ def read_alex_weights(lin_path, backbone_path):
 
 
 class AlexLPIPS:
-    """LPIPS v0.1 with the AlexNet trunk; parameters packed once on `device`.  A score only: there is no backward (the 11x11
-    stride-4 and 5x5 layers have no data-gradient kernel in the library); VggLPIPS.loss is the training loss."""
+    """LPIPS v0.1 with the AlexNet trunk; parameters packed once on `device`.  A score only: AlexLPIPSLoss adds the training
+    loss (and the weights its data gradients read); VggLPIPS.loss is the VGG-16 one."""
 
     def __init__(self, conv_w, conv_b, lin_w, device):
         self.device = torch.device(device)
@@ -127,12 +133,82 @@ class AlexLPIPS:
         return (out, layers) if per_layer else out
 
 
-def load_alex_lpips(lin_path, backbone_path, device="cuda", net=NET):
-    """AlexLPIPS from the reference's v0.1 heads (lin_path) and a torchvision AlexNet state dict (backbone_path)."""
+class AlexLPIPSLoss(AlexLPIPS):
+    """AlexLPIPS with `loss`: the reference's training term (perceptual_loss with its default net, train_ours.py:765).  Beside
+    the score's parameters it packs the conv weights in the layouts the data gradients read (ebfi_lpips_alex_pack_grad_params)."""
+
+    def __init__(self, conv_w, conv_b, lin_w, device):
+        super().__init__(conv_w, conv_b, lin_w, device)
+        h = N.lib()
+        nbytes = h.ebfi_lpips_alex_grad_params_bytes()
+        self.grad_params = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+        ws = self._keep[0]
+        with torch.cuda.device_of(self.grad_params):
+            rc = h.ebfi_lpips_alex_pack_grad_params((N._vp * 5)(*[t.data_ptr() for t in ws]), N.ptr(self.grad_params), nbytes,
+                                                    N.stream_ptr(self.device))
+        N.check(rc, "ebfi_lpips_alex_pack_grad_params")
+        self._train_pool = []
+
+    def _train_workspace(self, stream, shape):
+        """As VggLPIPS._train_workspace: one buffer per (stream, shape), a second only while two forwards await their backward,
+        nothing allocated inside a capture."""
+        return _take_train_workspace(self, stream, shape, N.lib().ebfi_lpips_alex_train_workspace,
+                                     "LPIPS (AlexNet): ebfi_lpips_alex_forward_train")
+
+    def _forward_train(self, pred, target, normalize, entry):
+        n, c, hgt, wid = (int(v) for v in pred.shape)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        with torch.cuda.device_of(pred):
+            rc = N.lib().ebfi_lpips_alex_forward_train(N.ptr(pred), N.i64x4(pred.stride()), N.ptr(target), N.i64x4(target.stride()),
+                                                       n, c, hgt, wid, 1 if normalize else 0, N.ptr(self.params), N.ptr(entry.buf),
+                                                       entry.buf.numel() * 8, N.ptr(out), None, N.stream_ptr(self.device))
+        N.check(rc, "ebfi_lpips_alex_forward_train")
+        return out
+
+    def _backward(self, grad_out, shape, normalize, entry):
+        n, c, hgt, wid = shape
+        grad_out = grad_out.to(torch.float32).contiguous()
+        grad_pred = torch.empty(shape, dtype=torch.float32, device=self.device)
+        with torch.cuda.device_of(grad_pred):
+            rc = N.lib().ebfi_lpips_alex_backward(N.ptr(grad_out), N.ptr(self.params), N.ptr(self.grad_params), N.ptr(entry.buf),
+                                                  entry.buf.numel() * 8, n, c, hgt, wid, 1 if normalize else 0, N.ptr(grad_pred),
+                                                  N.i64x4(grad_pred.stride()), N.stream_ptr(self.device))
+        N.check(rc, "ebfi_lpips_alex_backward")
+        return grad_pred
+
+    def loss(self, pred, target, normalize=True):
+        """lpips [N] of pred vs target as `__call__` returns it, bit for bit, with a graph: its backward is the gradient with
+        respect to pred (ebfi_lpips_alex_backward).  The target gets none, and one that requires grad is refused."""
+        if target.requires_grad:
+            raise ValueError("AlexLPIPSLoss.loss has no gradient for the target: pass target.detach() (got a target that requires "
+                             "grad)")
+        N.require_gpu(pred, target)
+        if pred.dim() != 4 or pred.shape != target.shape:
+            raise ValueError("LPIPS takes two [N, C, H, W] tensors of one shape, got %s and %s"
+                             % (tuple(pred.shape), tuple(target.shape)))
+        if pred.dtype != torch.float32 or target.dtype != torch.float32:
+            raise ValueError("LPIPS takes float32 tensors, got %s / %s" % (pred.dtype, target.dtype))
+        if pred.device != self.device or target.device != self.device:
+            raise ValueError("pred on %s, target on %s, weights on %s" % (pred.device, target.device, self.device))
+        c, hgt, wid = (int(v) for v in pred.shape[1:])
+        if c not in (1, 3):
+            raise ValueError("LPIPS takes 1 or 3 channels, got %d (loss.perceptual_loss averages other counts per channel)" % c)
+        if hgt < MIN_SIZE or wid < MIN_SIZE:
+            raise ValueError("LPIPS (AlexNet) needs H, W >= %d, got %d x %d" % (MIN_SIZE, hgt, wid))
+        pred = pred if pred.stride(3) == 1 else pred.contiguous()
+        target = target if target.stride(3) == 1 else target.contiguous()
+        if pred.shape[0] == 0:
+            return pred.new_zeros(0) + 0.0 * pred.sum()
+        return _TrainLoss.apply(pred, target, self, bool(normalize))
+
+
+def load_alex_lpips(lin_path, backbone_path, device="cuda", net=NET, train=False):
+    """AlexLPIPS from the reference's v0.1 heads (lin_path) and a torchvision AlexNet state dict (backbone_path); train=True:
+    AlexLPIPSLoss, the same score with `loss`."""
     if net != NET:
         raise NotImplementedError("LPIPS net=%r is not implemented: only 'alex' has device kernels here (the reference also "
                                   "offers 'vgg' and 'squeeze')" % (net,))
-    return AlexLPIPS(*read_alex_weights(lin_path, backbone_path), device)
+    return (AlexLPIPSLoss if train else AlexLPIPS)(*read_alex_weights(lin_path, backbone_path), device)
 
 
 # ------------------------------------------------------------------ the VGG-16 variant
@@ -233,19 +309,8 @@ class VggLPIPS:
         capture nothing should be allocated, and the capture runs on a stream of its own: it takes a free buffer of the shape
         whatever stream the eager passes before it left it on (every captured step here runs eagerly first).  A buffer that a
         captured graph replays on is kept for good and never handed to an eager call."""
-        capturing = torch.cuda.is_current_stream_capturing()
-        self._train_pool = [e for e in self._train_pool if e.shape == shape or e.captured]
-        for entry in self._train_pool:
-            if entry.shape == shape and entry.free() and (capturing or (entry.stream == stream and not entry.captured)):
-                entry.captured = entry.captured or capturing
-                return entry
-        nbytes = N.lib().ebfi_lpips_vgg_train_workspace(*shape)
-        if nbytes <= 0:
-            raise ValueError("LPIPS (VGG-16): ebfi_lpips_vgg_forward_train refuses the shape %s" % (shape,))
-        buf = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=self.device)
-        entry = _TrainWorkspace(buf, stream, shape, capturing)
-        self._train_pool.append(entry)
-        return entry
+        return _take_train_workspace(self, stream, shape, N.lib().ebfi_lpips_vgg_train_workspace,
+                                     "LPIPS (VGG-16): ebfi_lpips_vgg_forward_train")
 
     def _forward_train(self, pred, target, normalize, entry):
         n, c, hgt, wid = (int(v) for v in pred.shape)
@@ -278,7 +343,7 @@ class VggLPIPS:
         pred, target = self._check(pred, target)
         if pred.shape[0] == 0:
             return pred.new_zeros(0) + 0.0 * pred.sum()
-        return _VggLoss.apply(pred, target, self, bool(normalize))
+        return _TrainLoss.apply(pred, target, self, bool(normalize))
 
     @torch.no_grad()
     def __call__(self, pred, target, normalize=True, per_layer=False):
@@ -302,6 +367,23 @@ class VggLPIPS:
                                                 N.ptr(out[i:i + m]), N.ptr(layers[i:i + m]) if per_layer else None, stream)
                     N.check(rc, "ebfi_lpips_vgg")
         return (out, layers) if per_layer else out
+
+
+def _take_train_workspace(model, stream, shape, size_of, what):
+    """The pool rule of `model._train_pool` (VggLPIPS._train_workspace states it); `size_of(*shape)` is the entry point's size."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    model._train_pool = [e for e in model._train_pool if e.shape == shape or e.captured]
+    for entry in model._train_pool:
+        if entry.shape == shape and entry.free() and (capturing or (entry.stream == stream and not entry.captured)):
+            entry.captured = entry.captured or capturing
+            return entry
+    nbytes = size_of(*shape)
+    if nbytes <= 0:
+        raise ValueError("%s refuses the shape %s" % (what, shape))
+    buf = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=model.device)
+    entry = _TrainWorkspace(buf, stream, shape, capturing)
+    model._train_pool.append(entry)
+    return entry
 
 
 class _TrainWorkspace:
@@ -328,8 +410,8 @@ class _TrainWorkspace:
         self._owner = None
 
 
-class _VggLoss(torch.autograd.Function):
-    """lpips [N] of VggLPIPS.loss: ebfi_lpips_vgg_forward_train and ebfi_lpips_vgg_backward around one workspace."""
+class _TrainLoss(torch.autograd.Function):
+    """lpips [N] of VggLPIPS.loss / AlexLPIPSLoss.loss: the model's forward_train and backward around one workspace."""
 
     @staticmethod
     def forward(ctx, pred, target, model, normalize):
@@ -342,8 +424,8 @@ class _VggLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         if ctx.entry.generation != ctx.generation:
-            raise RuntimeError("VggLPIPS.loss: a later forward has overwritten the workspace of this one (its backward had "
-                               "already run once)")
+            raise RuntimeError("%s.loss: a later forward has overwritten the workspace of this one (its backward had "
+                               "already run once)" % type(ctx.model).__name__)
         grad_pred = ctx.model._backward(grad_out, ctx.shape, ctx.normalize, ctx.entry)
         ctx.entry.release()
         return grad_pred, None, None, None
@@ -357,10 +439,11 @@ def load_vgg_lpips(lin_path, backbone_path, device="cuda"):
 NETS = ("alex", "vgg")
 
 
-def load_lpips(net, lin_path, backbone_path, device="cuda"):
-    """The LPIPS model of `net`: 'alex' or 'vgg'.  'squeeze', the reference's third choice, has no device kernels here."""
+def load_lpips(net, lin_path, backbone_path, device="cuda", train=False):
+    """The LPIPS model of `net`: 'alex' or 'vgg'.  'squeeze', the reference's third choice, has no device kernels here.
+    train=True makes 'alex' an AlexLPIPSLoss (with `loss`); VggLPIPS has its `loss` either way."""
     if net == "alex":
-        return load_alex_lpips(lin_path, backbone_path, device=device)
+        return load_alex_lpips(lin_path, backbone_path, device=device, **({"train": True} if train else {}))
     if net == "vgg":
         return load_vgg_lpips(lin_path, backbone_path, device=device)
     raise NotImplementedError("LPIPS net=%r is not implemented: 'alex' and 'vgg' have device kernels here (the reference also "

@@ -27,16 +27,19 @@ class perceptual_loss:
     loss/PerceptualSimilarity/models/weights/v0.1/alex.pth, and backbone_path, torchvision's AlexNet state dict
     (alexnet-owt-7be5be79.pth); with net='vgg', v0.1/vgg.pth and torchvision's VGG-16 state dict (vgg16-397923af.pth).
     Without them it raises: no weight cache is searched.  net='squeeze' is refused.
-    With net='vgg', grad mode on and a pred that requires grad, the call is the reference's training loss: the value goes through
-    VggLPIPS.loss and differentiates into pred (the per-channel average of other channel counts too).  net='alex' is a score
-    only, with or without grad mode: its trunk has no data-gradient kernels."""
+    With net='vgg', grad mode on and a pred that requires grad, the call is a training loss: the value goes through
+    VggLPIPS.loss and differentiates into pred (the per-channel average of other channel counts too).  net='alex' -- the
+    reference's default, and what its trainer builds -- does the same when the object was made with train=True, which loads
+    AlexLPIPSLoss (the data-gradient weights are packed only then); without it net='alex' is a score, with or without grad mode."""
 
-    def __init__(self, weight=1.0, net='alex', use_gpu=True, gpu_ids=[0], lin_path=None, backbone_path=None):
+    def __init__(self, weight=1.0, net='alex', use_gpu=True, gpu_ids=[0], lin_path=None, backbone_path=None, train=False):
         if lin_path is None or backbone_path is None:
             raise NotImplementedError(LPIPS_UNAVAILABLE)
         from ebfi_amd.lpips import load_lpips
-        self.model = load_lpips(net, lin_path, backbone_path, device="cuda:%d" % gpu_ids[0])
+        extra = {"train": True} if train else {}
+        self.model = load_lpips(net, lin_path, backbone_path, device="cuda:%d" % gpu_ids[0], **extra)
         self.weight = weight
+        self.train_alex = net == 'alex' and bool(train)
 
     def __call__(self, pred, target, normalize=True):
         """pred, target: N x C x H x W; C == 1 and C == 3 in one call, any other C as the mean of per-channel calls, each channel
@@ -44,7 +47,7 @@ class perceptual_loss:
         assert pred.size() == target.size()
         c = pred.shape[1]
         model = self.model
-        if getattr(model, "NET", None) == "vgg" and torch.is_grad_enabled() and pred.requires_grad:
+        if (getattr(model, "NET", None) == "vgg" or self.train_alex) and torch.is_grad_enabled() and pred.requires_grad:
             model = model.loss                  # the training loss: the same value with a graph into pred
         if c in (1, 3):
             dist = model(pred, target, normalize=normalize)

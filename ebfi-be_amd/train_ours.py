@@ -21,9 +21,11 @@ model_best_until_iteration{it}.pth, and trainer.monitor_best travels through --r
 holds the rank-averaged values and takes the same decision.  The reference's TensorBoard log (:283-319, :594-616) is written by
 ebfi_amd.monitor into <output_path>/log/<experiment>/<runid>/ when trainer.tensorboard or --tensorboard asks for it (scalars;
 images with trainer.vis.enabled; per-layer weight / gradient statistics with trainer.telemetry.stats_step); off by default.
-The reference's perceptual_loss(net='vgg') (train_ours.py:765) is an optional term: `--lpips_weight W` (or trainer.lpips_weight)
-with `--lpips_lin` / `--lpips_backbone` adds W x LPIPS(Sharp, target), mean over the batch, to the loss above, differentiated by
-ebfi_amd.lpips on the device inside the (captured) step; the log line then names the term.  Off (W = 0) by default.
+The reference's perceptual_loss (train_ours.py:765; its net is the default of loss/restore.py:12, 'alex') is an optional term:
+`--lpips_weight W` (or trainer.lpips_weight) with `--lpips_lin` / `--lpips_backbone` adds W x LPIPS(Sharp, target), mean over the
+batch, to the loss above, differentiated by ebfi_amd.lpips on the device inside the (captured) step; the log line then names the
+term.  `--lpips_net {vgg,alex}` (or trainer.lpips_net) selects the trunk: vgg by default, alex for the reference's own.  Off
+(W = 0) by default.
 Two things the reference trains without, both off by default: `trainer.clip_grad: {max_norm, norm_type}` / `--clip-grad-norm X` clips
 every optimiser step's gradient by its total norm (norm_type 2 or inf) inside the update's launch -- the log line then shows
 grad_norm, the TensorBoard log `grad_norm/total` and `grad_norm/clip_coef` -- and `trainer.ema: {decay, warmup, validate}` /
@@ -119,18 +121,46 @@ def validation_settings(config, cli_valid_data=None):
             "dataset": vd.get("dataset") or {}}
 
 
+LPIPS_FILES = {"vgg": ("the v0.1 vgg.pth heads", "torchvision's VGG-16 state dict, vgg16-397923af.pth"),
+               "alex": ("the v0.1 alex.pth heads", "torchvision's AlexNet state dict, alexnet-owt-7be5be79.pth")}
+
+
+def perceptual_net(config, args):
+    """The trunk of the LPIPS term: --lpips_net, else trainer.lpips_net, else 'vgg'.  Any other name ends the run."""
+    tr = config.get("trainer", {}) or {}
+    flag = getattr(args, "lpips_net", None)
+    net = str(tr.get("lpips_net", "vgg") if flag is None else flag)
+    if net not in LPIPS_FILES:
+        raise SystemExit("train_ours.py: --lpips_net / trainer.lpips_net must be one of %s, got %r"
+                         % (", ".join(sorted(LPIPS_FILES)), net))
+    return net
+
+
 def perceptual_settings(config, args):
-    """(weight, lin_path, backbone_path) of the LPIPS (VGG-16) term of the training loss: --lpips_weight, else trainer.lpips_weight,
-    else 0 = off.  A positive weight without both weight files ends the run: no weight cache is searched."""
+    """(weight, lin_path, backbone_path) of the LPIPS term of the training loss: --lpips_weight, else trainer.lpips_weight,
+    else 0 = off.  A positive weight without both weight files ends the run: no weight cache is searched.  (The trunk is
+    perceptual_net's.)"""
     tr = config.get("trainer", {}) or {}
     weight = float(tr.get("lpips_weight", 0.0) if args.lpips_weight is None else args.lpips_weight)
     if weight < 0:
         raise SystemExit("train_ours.py: --lpips_weight / trainer.lpips_weight must not be negative, got %g" % weight)
+    heads, trunk = LPIPS_FILES[perceptual_net(config, args)]
     if weight > 0 and (args.lpips_lin is None or args.lpips_backbone is None):
         missing = " and ".join(f for f, v in (("--lpips_lin", args.lpips_lin), ("--lpips_backbone", args.lpips_backbone)) if v is None)
-        raise SystemExit("train_ours.py: an LPIPS weight of %g needs both weight files: --lpips_lin (the v0.1 vgg.pth heads) and "
-                         "--lpips_backbone (torchvision's VGG-16 state dict, vgg16-397923af.pth); missing %s" % (weight, missing))
+        raise SystemExit("train_ours.py: an LPIPS weight of %g needs both weight files: --lpips_lin (%s) and "
+                         "--lpips_backbone (%s); missing %s" % (weight, heads, trunk, missing))
     return weight, args.lpips_lin, args.lpips_backbone
+
+
+def perceptual_term(net, lin_path, backbone_path, weight, device):
+    """(PerceptualTerm, the log line's note) of a positive weight: VggLPIPS, or AlexLPIPSLoss for net = 'alex'."""
+    from ebfi_amd.loss import PerceptualTerm
+    from ebfi_amd.lpips import load_alex_lpips, load_vgg_lpips
+    if net == "alex":
+        model = load_alex_lpips(lin_path, backbone_path, device=device, train=True)
+    else:
+        model = load_vgg_lpips(lin_path, backbone_path, device=device)
+    return PerceptualTerm(model, weight), " (with %g x lpips_%s)" % (weight, net)
 
 
 def averaging_settings(config, args=None):
@@ -520,13 +550,18 @@ def get_args(argv=None):
                     help="build the event tensor from synthetic raw event lists with the device events_to_stack kernel "
                          "(the reference's data path, h5dataset.py:327-352) instead of drawing voxel counts directly")
     ap.add_argument("--lpips_weight", type=float, default=None,
-                    help="add W x LPIPS (VGG-16, v0.1; the reference's perceptual_loss(net='vgg')) of the restored frame to the "
+                    help="add W x LPIPS (v0.1; the reference's perceptual_loss) of the restored frame to the "
                          "training loss, differentiated on the device (default: trainer.lpips_weight of the config, else 0 = off); "
                          "needs --lpips_lin and --lpips_backbone")
+    ap.add_argument("--lpips_net", type=str, default=None,
+                    help="LPIPS: the trunk, vgg or alex (default: trainer.lpips_net of the config, else vgg; the reference "
+                         "trains with alex)")
     ap.add_argument("--lpips_lin", type=str, default=None,
-                    help="LPIPS: the reference's linear heads, loss/PerceptualSimilarity/models/weights/v0.1/vgg.pth")
+                    help="LPIPS: the reference's linear heads, loss/PerceptualSimilarity/models/weights/v0.1/vgg.pth (alex.pth "
+                         "with --lpips_net alex)")
     ap.add_argument("--lpips_backbone", type=str, default=None,
-                    help="LPIPS: torchvision's VGG-16 state dict (vgg16-397923af.pth of the torch hub cache)")
+                    help="LPIPS: torchvision's VGG-16 state dict (vgg16-397923af.pth of the torch hub cache; "
+                         "alexnet-owt-7be5be79.pth with --lpips_net alex)")
     add_loader_arguments(ap)
     add_monitor_arguments(ap)
     add_averaging_arguments(ap)
@@ -537,7 +572,8 @@ def main(argv=None):
     args = get_args(argv)
     with open(args.config) as fh:
         config = yaml.safe_load(fh)
-    lpips_weight, lpips_lin, lpips_backbone = perceptual_settings(config, args)      # (refuses before any device work)
+    lpips_net = perceptual_net(config, args)                                          # (refuses before any device work)
+    lpips_weight, lpips_lin, lpips_backbone = perceptual_settings(config, args)      # (likewise)
     optimizer = optimizer_settings(config, args)                                      # (likewise)
     averaging = averaging_settings(config, args)                                      # (likewise)
     tr = config.get("trainer", {}) or {}
@@ -550,10 +586,7 @@ def main(argv=None):
 
     perceptual, loss_note = None, ""
     if lpips_weight > 0:
-        from ebfi_amd.loss import PerceptualTerm
-        from ebfi_amd.lpips import load_vgg_lpips
-        perceptual = PerceptualTerm(load_vgg_lpips(lpips_lin, lpips_backbone, device=device), lpips_weight)
-        loss_note = " (with %g x lpips_vgg)" % lpips_weight
+        perceptual, loss_note = perceptual_term(lpips_net, lpips_lin, lpips_backbone, lpips_weight, device)
     eng = Engine(config["model"]["args"], device=device, precision=args.precision, optimizer=optimizer,
                  seed=args.seed,                                                      # same init on every rank
                  graph=args.graph or bool(tr.get("graph", False)), accu_step=st["accu_step"],

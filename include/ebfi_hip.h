@@ -57,7 +57,8 @@
  *   ebfi_avgpool2_forward / ebfi_bilinear_up2_forward / ebfi_flow_max_magnitude / ebfi_slomo_*
  *                               the Vid2E adaptive upsampler (generate_dataset/upsampling/utils/{upsampler,model}.py)
  *   ebfi_image_metrics          psnr_loss / ssim_loss / nn.MSELoss of the evaluation loop (loss/restore.py:43-92, infer_ours.py:120-128)
- *   ebfi_lpips_*                perceptual_loss(net='alex') of the evaluation loop (loss/restore.py:10-40, LPIPS v0.1)
+ *   ebfi_lpips_*                perceptual_loss(net='alex') of the evaluation loop (loss/restore.py:10-40, LPIPS v0.1) and, as
+ *                               ebfi_lpips_alex_forward_train / _backward, of the training loss (train_ours.py:765)
  *   ebfi_lpips_vgg*             perceptual_loss(net='vgg'), likewise
  *   ebfi_charbonnier_*          CharbonnierLoss of the validation loop (loss/restore.py:95-105, train_ours.py:588)
  *   ebfi_duty_head_*            tail of ExposureDecision.forward + nn.MSELoss of stage 1 (model_singleframe.py:75-76,
@@ -117,7 +118,9 @@ extern "C" {
  *      ebfi_gather_sum_multi (their fold gathers), likewise; and ebfi_event_augment / ebfi_event_hot_pixels (the device noise
  *      law of the clip loaders), likewise; and ebfi_dcn_pooling_forward / _backward (the deformable PS-ROI pooling of the
  *      DCNv2 package), likewise; and ebfi_grad_norm_workspace / ebfi_grad_norm / ebfi_optim_step_ex (gradient clipping by
- *      total norm and an exponential moving average of the weights around the optimiser step), likewise */
+ *      total norm and an exponential moving average of the weights around the optimiser step), likewise; and
+ *      ebfi_lpips_alex_grad_params_bytes / _pack_grad_params / _train_workspace / _forward_train / _backward (evaluation LPIPS
+ *      with the AlexNet trunk as a training loss), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -883,7 +886,8 @@ int ebfi_lpips_vgg(const float *pred, const int64_t pred_strides[4], const float
                    float *out_lpips, float *out_layers, void *stream);
 
 /* ------------------------------------------------------------------ LPIPS (VGG-16, v0.1) as a training loss
- * The reference's perceptual_loss(net='vgg') is a loss (train_ours.py:765): autograd carries it into the prediction.  Here
+ * The reference's perceptual_loss is a loss (train_ours.py:765 builds it with its default trunk, net='alex'; this is the same loss
+ * with net='vgg'): autograd carries it into the prediction.  Here
  * ebfi_lpips_vgg_forward_train takes the arguments of ebfi_lpips_vgg and writes the same out_lpips / out_layers, bit for bit
  * (the same kernels on the same values in the same order of sums: each image's convolution tiles do not depend on the batch they
  * are launched in), and keeps in `workspace` (at least ebfi_lpips_vgg_train_workspace(N, C, H, W) bytes, pure host arithmetic, 0
@@ -910,14 +914,60 @@ int ebfi_lpips_vgg(const float *pred, const int64_t pred_strides[4], const float
  * for C == 3, the sum over the three c for C == 1.  A pair whose pred or target held a NaN or Inf (the forward's flags) gets
  * grad_pred[n] NaN everywhere; no other pair is touched by it.
  * Both follow the launch contract of ebfi_lpips_alex (on `stream` only, no host synchronisation, no allocation, no atomics:
- * capturable and bit-reproducible) and its error codes; argument errors touch no GPU.  The AlexNet trunk stays forward-only: its
- * 11x11 stride-4 and 5x5 layers have no data-gradient kernel here. */
+ * capturable and bit-reproducible) and its error codes; argument errors touch no GPU.  The AlexNet trunk's training form is the
+ * next section. */
 int64_t ebfi_lpips_vgg_train_workspace(int64_t N, int C, int H, int W);
 int ebfi_lpips_vgg_forward_train(const float *pred, const int64_t pred_strides[4], const float *target,
                                  const int64_t target_strides[4], int64_t N, int C, int H, int W, int normalize, const void *params,
                                  void *workspace, int64_t workspace_bytes, float *out_lpips, float *out_layers, void *stream);
 int ebfi_lpips_vgg_backward(const float *grad_out, const void *params, void *workspace, int64_t workspace_bytes, int64_t N, int C,
                             int H, int W, int normalize, float *grad_pred, const int64_t grad_pred_strides[4], void *stream);
+
+/* ------------------------------------------------------------------ LPIPS (AlexNet, v0.1) as a training loss
+ * The trunk the reference trains with: its trainer builds perceptual_loss(gpu_ids=[local_rank]) (train_ours.py:765), and 'alex'
+ * is the default net of loss/restore.py:12.  ebfi_lpips_alex_forward_train takes the arguments of ebfi_lpips_alex and writes the
+ * same out_lpips / out_layers, bit for bit: it launches the same kernels on the same values, and the front of its workspace (at
+ * least ebfi_lpips_alex_train_workspace(N, C, H, W) bytes, pure host arithmetic, 0 for a shape ebfi_lpips_alex refuses) is the
+ * score's workspace -- f1 .. f5 of all 2N images, the tile partials and the non-finite flags -- followed by the two gradient
+ * maps of the pred images that the backward alternates between (each as large as the largest of f1 .. f5 of N images).
+ * (57.2 MB for 8 pairs of 256 x 256, 105.1 MB for one 720 x 1280 pair: the score's 41.0 / 75.9 MB and the two maps.)
+ *
+ * ebfi_lpips_alex_backward reads that workspace (of the forward_train call with the same N, C, H, W, normalize and params; it
+ * writes the gradient maps into it, so one backward per forward) and grad_out, device float[N], and fully overwrites grad_pred
+ * [N, C, H, W] fp32 through grad_pred_strides (elements; column stride 1).  The target gets no gradient.  The gradient's
+ * definition is that of ebfi_lpips_vgg_backward above -- n0, r0, a_c, S, dL/dx_k, exactly 0 where n0 == 0, the sums in fp64 from
+ * the fp32 maps -- with AlexNet's trunk around it.  Launches, pred images only:
+ *   tap adjoint x5    sixteen threads per pixel of a tap map: the distance gradient, plus the gradient that arrives from the next
+ *                     block.  For f3 and f4 that is a map of the same size; for f1 and f2 it is the gradient of the 3x3 / stride 2
+ *                     pooled map, gathered: a pixel lies in at most 2 x 2 windows, and a window's gradient is added if and only if
+ *                     the pixel is the window's first maximum in row-major order (torch's rule), found again from the kept map --
+ *                     no pooled map and no argmax is stored, and no atomics are used.  Rows and columns past the last window get
+ *                     a tap gradient and no routed one.
+ *   conv5 .. conv2    one kernel of lpips.hip, an implicit GEMM on exact fp32 MFMA (v_mfma_f32_32x32x2_f32) with the taps
+ *                     flipped: K = 256 x 9, 256 x 9, 384 x 9 and, for the 5x5 layer, 192 x 25; the gradient patch of an 8 x 8 tile
+ *                     staged in LDS as the forward stages its input, the ReLU mask of the kept output applied on the way
+ *   conv1 (11x11/s4)  a direct fp32 kernel in a fixed order of sums: input row i = 4 q + r - 2 takes the taps k = 4 d + r of the
+ *                     output rows q - d, d in {0, 1, 2}, so a thread keeps the 3 x 3 x 3 weights of one phase (r_y, r_x) and
+ *                     one output channel in registers for four pixels.  Its epilogue is the input epilogue: with mul_c =
+ *                     (normalize ? 2 : 1) / scale_c, grad_pred[n, c] = mul_c * grad_x'[n, c] for C == 3, the sum over the three c
+ *                     for C == 1.  An input row or column that no conv1 window covers (row 33 of a 34-row image) gets exactly 0.
+ * A pair whose pred or target held a NaN or Inf (the forward's flags) gets grad_pred[n] NaN everywhere; no other pair is touched
+ * by it.  Exact fp32 in the convolutions, fp64 in the tap sums; no bf16 or fp16 operand.
+ * grad_params (16-byte aligned, at least ebfi_lpips_alex_grad_params_bytes() bytes) holds the five conv weights in the layouts
+ * the data gradients stage from -- conv1 as given ([64][3][11][11]), conv2 .. conv5 as the flipped implicit-GEMM image
+ * [Cout][k][k][Cin] -- packed once by ebfi_lpips_alex_pack_grad_params from a host array of 5 device pointers (the
+ * conv_w of ebfi_lpips_pack_params).  `params` stays what ebfi_lpips_pack_params wrote: its size and bits do not change.
+ * The launch contract is ebfi_lpips_alex's (on `stream` only, no host synchronisation, no allocation, no atomics: capturable and
+ * bit-reproducible), and so are the shape limits (H, W >= 31) and the error codes; argument errors touch no GPU. */
+int64_t ebfi_lpips_alex_grad_params_bytes(void);
+int ebfi_lpips_alex_pack_grad_params(const float *const *conv_w, void *grad_params, int64_t bytes, void *stream);
+int64_t ebfi_lpips_alex_train_workspace(int64_t N, int C, int H, int W);
+int ebfi_lpips_alex_forward_train(const float *pred, const int64_t pred_strides[4], const float *target,
+                                  const int64_t target_strides[4], int64_t N, int C, int H, int W, int normalize, const void *params,
+                                  void *workspace, int64_t workspace_bytes, float *out_lpips, float *out_layers, void *stream);
+int ebfi_lpips_alex_backward(const float *grad_out, const void *params, const void *grad_params, void *workspace,
+                             int64_t workspace_bytes, int64_t N, int C, int H, int W, int normalize, float *grad_pred,
+                             const int64_t grad_pred_strides[4], void *stream);
 
 /* ------------------------------------------------------------------ Charbonnier loss (validation)
  * CharbonnierLoss of the reference (loss/restore.py:95-105; the validation score of train_ours.py:588) per sample n of an fp32

@@ -16,6 +16,11 @@ depend on the weights).  Prints one JSON line per shape: microseconds per call, 
                         alone and its share, the training workspace, and -- as context: it is what the reference runs -- PyTorch
                         eager autograd through the same trunk (F.conv2d / F.max_pool2d / F.relu in float32) on the same device
 
+  --net alex --backward the same rows for AlexLPIPSLoss.loss (ebfi_lpips_alex_forward_train / _backward): step, forward alone,
+                        backward (the difference), score, the training workspace, per-kernel rows from the event profiler (the
+                        five tap adjoints, the MFMA data gradients of conv5 .. conv2 and the direct 11x11 stride-4 kernel
+                        with its input epilogue), and PyTorch eager autograd through the AlexNet trunk
+
 usage: python tools/lpipsbench.py [iters] [--net {alex,vgg}] [--backward]"""
 import argparse
 import json
@@ -27,7 +32,7 @@ sys.path.insert(0, os.path.join(ROOT, "ebfi-be_amd"))
 import torch  # noqa: E402
 
 from ebfi_amd import _native as N  # noqa: E402
-from ebfi_amd.lpips import CONV_SHAPES, VGG_CONV_SHAPES, VGG_HEAD_CHANNELS, AlexLPIPS, VggLPIPS  # noqa: E402
+from ebfi_amd.lpips import CONV_SHAPES, VGG_CONV_SHAPES, VGG_HEAD_CHANNELS, AlexLPIPS, AlexLPIPSLoss, VggLPIPS  # noqa: E402
 
 FP32_MATRIX_PEAK = 157.3e12
 
@@ -136,14 +141,14 @@ def time_steps(step, iters):
     return dict(us_mean=round(sum(us) / len(us), 1), us_min=round(min(us), 1), us_max=round(max(us), 1))
 
 
-def torch_eager_loss(ws, bs, hs, pred, target):
+def torch_eager_loss(ws, bs, hs, pred, target, net="vgg"):
     """The reference's path: the same trunk and distances as torch ops in float32 (normalize=True), lpips [N]."""
     import torch.nn.functional as F
     shift = torch.tensor([-0.030, -0.088, -0.188], device=pred.device).view(1, 3, 1, 1)
     scale = torch.tensor([0.458, 0.448, 0.450], device=pred.device).view(1, 3, 1, 1)
     blocks = (2, 2, 3, 3, 3)
 
-    def taps(x):
+    def vgg_taps(x):
         x, out, i = (2 * x - 1 - shift) / scale, [], 0
         for k, n in enumerate(blocks):
             if k:
@@ -154,6 +159,15 @@ def torch_eager_loss(ws, bs, hs, pred, target):
             out.append(x)
         return out
 
+    def alex_taps(x):
+        x = (2 * x - 1 - shift) / scale
+        f1 = F.relu(F.conv2d(x, ws[0], bs[0], stride=4, padding=2))
+        f2 = F.relu(F.conv2d(F.max_pool2d(f1, 3, 2), ws[1], bs[1], padding=2))
+        f3 = F.relu(F.conv2d(F.max_pool2d(f2, 3, 2), ws[2], bs[2], padding=1))
+        f4 = F.relu(F.conv2d(f3, ws[3], bs[3], padding=1))
+        return [f1, f2, f3, f4, F.relu(F.conv2d(f4, ws[4], bs[4], padding=1))]
+
+    taps = alex_taps if net == "alex" else vgg_taps
     unit = lambda f: f / (torch.sqrt((f ** 2).sum(1, keepdim=True)) + 1e-10)     # noqa: E731
     with torch.no_grad():
         t_taps = taps(target)
@@ -161,6 +175,42 @@ def torch_eager_loss(ws, bs, hs, pred, target):
     for f0, f1, h in zip(taps(pred), t_taps, hs):
         total = total + (h.view(1, -1, 1, 1) * (unit(f0) - unit(f1)) ** 2).sum(1).mean((1, 2))
     return total
+
+
+def bench_alex_backward(alex, weights, N_, C, H, W, iters):
+    pred, target = pair(N_, C, H, W)
+    pred.requires_grad_(True)
+
+    def step():
+        pred.grad = None
+        alex.loss(pred, target).sum().backward()
+
+    def forward_only():
+        with torch.no_grad():
+            alex.loss(pred, target)
+
+    row = dict(net="alex", mode="forward_train+backward", shape=[N_, C, H, W],
+               train_workspace_bytes=int(N.lib().ebfi_lpips_alex_train_workspace(N_, C, H, W)),
+               score_workspace_bytes=int(N.lib().ebfi_lpips_workspace(N_, C, H, W)))
+    row["step"] = time_steps(step, iters)
+    row["forward_train"] = time_steps(forward_only, iters)
+    row["score"] = time_steps(lambda: alex(pred.detach(), target), iters)
+    row["backward_us"] = round(row["step"]["us_mean"] - row["forward_train"]["us_mean"], 1)
+
+    class Both:                                    # (kernel_rows calls model(pred, target))
+        def __call__(self, p, t):
+            step()
+
+    row["kernels"] = kernel_rows(Both(), pred, target, min(iters, 3))
+    ws, bs, hs = ([t.to("cuda") for t in part] for part in weights)
+
+    def eager_step():
+        pred.grad = None
+        torch_eager_loss(ws, bs, hs, pred, target, net="alex").sum().backward()
+
+    row["torch_eager_step"] = time_steps(eager_step, iters)
+    print(json.dumps(row), flush=True)
+    return row
 
 
 def bench_vgg_backward(vgg, weights, N_, C, H, W, iters):
@@ -227,13 +277,17 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("iters", type=int, nargs="?", default=10)
     ap.add_argument("--net", choices=("alex", "vgg"), default="alex")
-    ap.add_argument("--backward", action="store_true", help="with --net vgg: time the training loss (forward_train + backward)")
+    ap.add_argument("--backward", action="store_true", help="time the training loss (forward_train + backward)")
     a = ap.parse_args()
-    if a.backward and a.net != "vgg":
-        ap.error("--backward needs --net vgg: the AlexNet trunk is forward-only")
     assert torch.cuda.is_available(), "lpipsbench needs the MI355X"
     g = torch.Generator().manual_seed(0)
-    alex = AlexLPIPS(*random_weights(CONV_SHAPES, [s[0] for s in CONV_SHAPES], g), "cuda")
+    alex_weights = random_weights(CONV_SHAPES, [s[0] for s in CONV_SHAPES], g)
+    if a.net == "alex" and a.backward:
+        loss_model = AlexLPIPSLoss(*alex_weights, "cuda")
+        bench_alex_backward(loss_model, alex_weights, 8, 3, 256, 256, a.iters)
+        bench_alex_backward(loss_model, alex_weights, 1, 3, 720, 1280, a.iters)
+        sys.exit(0)
+    alex = AlexLPIPS(*alex_weights, "cuda")
     if a.net == "alex":
         bench(alex, 16, 3, 720, 1280, a.iters)
         bench(alex, 16, 3, 256, 256, a.iters)
