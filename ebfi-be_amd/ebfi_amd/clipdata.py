@@ -258,8 +258,15 @@ class ClipDataset:
 
     def __init__(self, paths, time_bins=16, frames_per_period=16, frames_per_blurry=16, exposure_method="Fixed",
                  exposure_time=None, crop=None, crop_mode="random", flips=False, device="cuda", seed=0,
-                 flip_probs=(0.5, 0.5), center_crop=None, noise=None, frames="host", noise_mode="host", hot_pixels=None):
-        """crop / crop_mode: the first crop of AugmentData's list (RandomCrop when enabled, else CenterCrop); center_crop: a
+                 flip_probs=(0.5, 0.5), center_crop=None, noise=None, frames="host", noise_mode="host", hot_pixels=None,
+                 neighbours=False):
+        """neighbours (the reference's NeedNeighborGT, h5dataset.py:138-147, 219-271): an item also carries
+        SeqNeighborF [1, 1, NumF, 2, 3, H, W], the ground-truth neighbours of every latent frame -- what the STGAN adversarial
+        loss takes as `input_frames`: neighbour 0 of latent i is latent max(i - 1, 0), neighbour 1 is latent min(i + 1, NumF - 1),
+        of the same period.  The reference reads those frames a second time and augments them with the item's seed, i.e. with
+        the window and flips of the latent frames; here they are gathers of the finished latent tensor on the device, in both
+        loader modes: no extra frame is read or uploaded.
+        crop / crop_mode: the first crop of AugmentData's list (RandomCrop when enabled, else CenterCrop); center_crop: a
         CenterCrop applied AFTER a random crop when the config enables both (the reference walks its `augment` list in order,
         h5dataset.py:410-433); flip_probs: (horizontal_prob, vertical_prob) of data_augment.flip; noise: None or
         (noise_std, noise_fraction) of data_augment.noise -- applied to the event stack after crops and flips with the item's
@@ -278,6 +285,7 @@ class ClipDataset:
             raise ValueError("frames must be 'host' or 'device', got %r" % (frames,))
         self.frames = frames
         self.noise_mode = noise_mode
+        self.neighbours = bool(neighbours)
         self.noise_table, self.hot_pixels = noise_law(noise_mode, self.noise, hot_pixels)
         self.items = []
         for ci, clip in enumerate(self.clips):
@@ -326,9 +334,12 @@ class ClipDataset:
         dev = stack.device
         rel_ts = (torch.arange(self.P) / self.P).to(dev)      # integer tensor / int on the HOST, like GetTimestamp (a device
         #                                                       division may differ in the last bit)
-        return {"SeqLatentF": sharp[None, None].contiguous(), "SeqBlurryF": blur[None, None].contiguous(),
+        item = {"SeqLatentF": sharp[None, None].contiguous(), "SeqBlurryF": blur[None, None].contiguous(),
                 "SeqHREv": stack[None].contiguous(), "RelativeLatentTs": rel_ts[None, None],
                 "SeqExposureDuty": torch.tensor([[[duty]]], dtype=torch.float32, device=dev)}
+        if self.neighbours:
+            item["SeqNeighborF"] = neighbour_frames(sharp)[None, None].contiguous()
+        return item
 
     def window(self, resolution, seed):
         """(i, j, h, w): the crops `augment` applies for this seed, composed into one window of the frame (the whole frame
@@ -520,6 +531,19 @@ class RealBlurClipDataset:
 SUPPORTED_AUGMENT_ORDER = ["RandomCrop", "CenterCrop", "HorizontalFlip", "VertivcalFlip", "Noise", "HotPixel"]
 
 
+def neighbour_indices(num_frames):
+    """[NumF, 2]: the latent indices of a period's neighbours -- (max(i - 1, 0), min(i + 1, NumF - 1)) for latent i
+    (h5dataset.py:138-147)."""
+    i = torch.arange(int(num_frames))
+    return torch.stack([(i - 1).clamp_min(0), (i + 1).clamp_max(int(num_frames) - 1)], 1)
+
+
+def neighbour_frames(sharp):
+    """sharp [NumF, 3, H, W] (a period's latent frames, cropped and flipped) -> [NumF, 2, 3, H, W], gathered where `sharp` lives."""
+    idx = neighbour_indices(sharp.shape[0]).to(sharp.device)
+    return sharp.index_select(0, idx.reshape(-1)).reshape((sharp.shape[0], 2) + tuple(sharp.shape[1:]))
+
+
 def dataset_args_from_config(ds_cfg, hot_pixels=False):
     """The reference's `train_dataloader.dataset` keys (config/train_ours.yml:115-150) -> ClipDataset keyword arguments.
     Everything the keys can ask for that this reader does NOT do is refused here instead of being ignored silently
@@ -530,6 +554,12 @@ def dataset_args_from_config(ds_cfg, hot_pixels=False):
     device (noise_mode="device")."""
     aug = ds_cfg.get("data_augment") or {}
     out = dict(crop=None, crop_mode="random", center_crop=None, flips=False, flip_probs=(0.5, 0.5), noise=None)
+    if ds_cfg.get("NeedNeighborGT"):
+        # (the key is only handed on when set: the other dataset classes these arguments reach have no neighbours)
+        if ds_cfg.get("DeblurPretrain"):
+            raise NotImplementedError("dataset.NeedNeighborGT with DeblurPretrain: the reference then keeps one latent frame per "
+                                      "period but the neighbours of all of them; that combination is not implemented")
+        out["neighbours"] = True
     # the tensors the model sees come from the reference's `gt_prex` groups (h5dataset.py:36-100): 'ori' exactly when `scale`
     # equals the factor `ori_scale` names -- the shipped pair (2, 'down2') and (1, 'ori') among them; any other pair reads
     # down-scaled groups this reader does not open
@@ -663,14 +693,18 @@ def eval_batches(dataset, batch_size, rank=0, world=1, seed=0, drop_last=False, 
 
 def model_inputs(batch):
     """The reference's loop over one collated batch (train_ours.py:226-251, L = NumP = 1): yields
-    (Frame [B,3,H,W], Event [B,TB,2,H,W], T [B,1], GTEx [B,1], LatentF [B,3,H,W]) per latent frame."""
+    (Frame [B,3,H,W], Event [B,TB,2,H,W], T [B,1], GTEx [B,1], LatentF [B,3,H,W]) per latent frame -- and, when the batch carries
+    SeqNeighborF (dataset.NeedNeighborGT), NeighborF [B,2,3,H,W] as a sixth item: the slice the reference's loop keeps commented
+    out (train_ours.py:228, 239, 247), the `input_frames` of its Adversarial."""
     latent = batch["SeqLatentF"][:, 0, 0]                 # [B, NumF, 3, H, W]
+    neighbour = batch["SeqNeighborF"][:, 0, 0] if "SeqNeighborF" in batch else None       # [B, NumF, 2, 3, H, W]
     frame = batch["SeqBlurryF"][:, 0, 0].contiguous()
     event = batch["SeqHREv"][:, 0].contiguous()
     ts = batch["RelativeLatentTs"][:, 0, 0]               # [B, NumF]
     duty = batch["SeqExposureDuty"][:, 0, 0].contiguous()  # [B, 1]
     for i in range(ts.shape[-1]):
-        yield frame, event, ts[:, [i]].contiguous(), duty, latent[:, i].contiguous()
+        item = (frame, event, ts[:, [i]].contiguous(), duty, latent[:, i].contiguous())
+        yield item if neighbour is None else item + (neighbour[:, i].contiguous(),)
 
 
 def write_synthetic_clip(path, num_imgs=33, H=64, W=64, events_per_frame=400, seed=0, exposure_stamps=False):

@@ -85,7 +85,8 @@ def synthetic_validation_batch(B, H, W, TB=16, num_frames=4, device="cuda", seed
 class Engine(graphstep.GraphStepper):
     def __init__(self, model_args=None, device="cuda", precision="fp32", lr=1e-4, seed=None, train=True, graph=False,
                  accu_step=1, betas=(0.9, 0.999), backward_f16=None, forward_f16="filters", strict_graph=None,
-                 perceptual=None, optimizer=None, defer_wgrad=True, defer_wgrad_cap=None, clip_grad=None, ema=None):
+                 perceptual=None, optimizer=None, defer_wgrad=True, defer_wgrad_cap=None, clip_grad=None, ema=None,
+                 adversarial=None):
         """graph / accu_step / strict_graph: see graphstep.GraphStepper (a graph is captured per input shape, precision and loss
         phase).
         optimizer: None = Adam with `lr` / `betas` (the shipped config), or the config's optimizer section {"name": "Adam" |
@@ -98,6 +99,12 @@ class Engine(graphstep.GraphStepper):
         perceptual: None, or an ebfi_amd.loss.PerceptualTerm: its value for (Sharp, target), / accu_step, is added to the training
         loss before the backward pass, inside the captured step.  The LPIPS weights are not model parameters: they are neither
         trained nor saved.  With None not one launch of the step changes.
+        adversarial: None, or an ebfi_amd.gan.AdversarialTerm (the reference's 'GAN': Adversarial(gan_type='STGAN') entry): its
+        value for (Sharp, target, neighbours), / accu_step, is added to the training loss before the backward pass, inside the
+        captured step; `train_step` then takes the neighbours [B, 2, 3, H, W] as a sixth input.  Every call -- every micro-step,
+        as the reference's call order implies -- also takes the discriminator's own Adamax step; `eng.adversarial.loss_d` is its
+        loss as a device scalar.  The discriminator is initialised identically on every rank and then trains per rank without
+        a collective (the reference does not wrap Adversarial in DDP).  With None not one launch of the step changes.
         forward_f16 (only with the fp16 backward; ignored otherwise): which FORWARD convolutions read fp16 operand images (one matrix-core product per
         tap, fp32 accumulation) instead of running in split precision:
           "filters"  the 128 -> 1600 KernelConv of Modification, whose output exists only as fp16 planes anyway (ebfi_amd.fac):
@@ -133,6 +140,11 @@ class Engine(graphstep.GraphStepper):
         self.calibration_steps = 2
         self.defer_wgrad, self.defer_wgrad_cap = bool(defer_wgrad), defer_wgrad_cap
         self.perceptual = perceptual if train else None
+        self.adversarial_term = adversarial if train else None
+        self.adversarial = None
+        if self.adversarial_term is not None:
+            self.adversarial = self.adversarial_term.adversarial.to(self.device)
+            broadcast_parameters(self.adversarial, 0)
         # ebfi_amd.monitor (images on): sample 0 of the restored frame of every pass is kept in `panel_sharp` -- one small copy inside
         # the (captured) step -- and `validate` leaves (Frame, Event, last Final, last LatentF) in `last_valid_panels`.  Off by
         # default: not one launch of the step changes.  Set before the first step (a graph holds what it was captured with).
@@ -179,7 +191,10 @@ class Engine(graphstep.GraphStepper):
             return contextlib.nullcontext()
         return self.book.active()
 
-    def _fwd_bwd(self, frame, event, t, gtex, target):
+    def _fwd_bwd(self, frame, event, t, gtex, target, neighbours=None):
+        if (neighbours is None) != (self.adversarial_term is None):
+            raise ValueError("train_step takes the neighbours [B, 2, 3, H, W] as a sixth input exactly when the engine was built "
+                             "with adversarial=")
         from . import wgradqueue
         cap = wgradqueue.BYTE_CAP if self.defer_wgrad_cap is None else self.defer_wgrad_cap
         with self._autocast(), self._bank(), self._book() as book, \
@@ -194,6 +209,8 @@ class Engine(graphstep.GraphStepper):
             loss = self.loss(sharp_pre.float(), sharp.float(), target, self.iteration, self.accu_step)
             if self.perceptual is not None:
                 loss = loss + self.perceptual(sharp.float(), target) / self.accu_step
+            if self.adversarial_term is not None:
+                loss = loss + self.adversarial_term(sharp.float(), target, neighbours) / self.accu_step
             loss.backward()
             if queue is not None:
                 queue.flush()                       # (before the finish: its launches record operand maxima the finish reads)
@@ -217,7 +234,18 @@ class Engine(graphstep.GraphStepper):
         return self.book is not None and self.precision == "bf16x3" and self._steps_run < self.calibration_steps
 
     def _graph_key(self):
+        if self.adversarial is not None:
+            # (the discriminator's Adamax launch is inside the captured step and takes its lr by value: a scheduler's new
+            #  value gets a graph of its own instead of being ignored by the replay)
+            return (self.iteration < 10e3, self.adversarial.lr)
         return (self.iteration < 10e3,)                    # TrainLoss switches its weighting at 10k iterations
+
+    def _capture_snapshot(self):
+        # the warm-up passes of a capture are discriminator steps on this batch: they must not count
+        return None if self.adversarial is None else self.adversarial.snapshot()
+
+    def _capture_restore(self, snapshot):
+        self.adversarial.restore(snapshot)
 
     def _before_first_capture(self):
         if self.bank is not None:

@@ -75,6 +75,14 @@ class GraphStepper:
     def _before_first_capture(self):
         """Runs once, ahead of the warm-up passes of the engine's first capture."""
 
+    def _capture_snapshot(self):
+        """State besides the guard that the warm-up passes of a capture change and that must be as found once the graph is
+        taken (an engine whose pass trains something of its own); None: nothing."""
+        return None
+
+    def _capture_restore(self, snapshot):
+        """Puts back what `_capture_snapshot` returned (called only with a snapshot that is not None)."""
+
     def _publish(self, out, static):
         """`out`: what `_fwd_bwd` returned -> the loss `train_step` returns.  static: `out` is a graph's output buffer, which the
         next replay overwrites: hand out a copy."""
@@ -233,6 +241,7 @@ class GraphStepper:
             # passes measured on this batch (restoring them could undo the just-in-time calibration of a slot first met here).
             guard = self._guard()
             saved = None if guard is None else guard.clone()
+            snapshot = self._capture_snapshot()
             if not self._graphs:
                 self._before_first_capture()
 
@@ -248,6 +257,9 @@ class GraphStepper:
                 if saved is not None:
                     torch.cuda.synchronize(self.device)
                     guard.copy_(saved)
+                if snapshot is not None:
+                    torch.cuda.synchronize(self.device)
+                    self._capture_restore(snapshot)
                 if self.strict_graph:
                     raise RuntimeError("%s: hipGraph capture failed and strict_graph is set (the default for one rank of "
                                        "several): %s" % (name, reason)) from err
@@ -259,6 +271,8 @@ class GraphStepper:
                 return self.train_step(*inputs)
             if saved is not None:
                 guard.copy_(saved)
+            if snapshot is not None:
+                self._capture_restore(snapshot)
             entry = self._graphs[key] = (graph, static_in, out, wire, [p.grad for p in self.bucket.params])
         graph, static_in, out, wire, grads = entry
         self._begin_micro_step()

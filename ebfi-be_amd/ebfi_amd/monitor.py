@@ -216,6 +216,11 @@ class TrainMonitor:
         self._meta = []
         return self.last_train_loss
 
+    def scalar(self, tag, value, step):
+        """One further scalar (a host value the caller read at a log step), written by the writer thread on rank 0."""
+        if self.writer is not None:
+            self._jobs.submit(None, lambda: self.writer.add_scalar(tag, float(value), int(step)))
+
     def pause(self, seconds):
         """Takes time that was not training (a validation stamp) off the interval steps_per_sec averages over."""
         self._mark += seconds

@@ -26,6 +26,13 @@ The reference's perceptual_loss (train_ours.py:765; its net is the default of lo
 batch, to the loss above, differentiated by ebfi_amd.lpips on the device inside the (captured) step; the log line then names the
 term.  `--lpips_net {vgg,alex}` (or trainer.lpips_net) selects the trunk: vgg by default, alex for the reference's own.  Off
 (W = 0) by default.
+The reference's 'GAN' entry (train_ours.py:767: Adversarial(PatchSize=<crop>, gan_type='STGAN')) is an optional term too:
+`--gan_weight W` (or trainer.gan: {weight, type: STGAN}) adds W x the generator's loss under a spatio-temporal patch discriminator
+that every pass also trains by its own Adamax step (ebfi_amd.gan), inside the (captured) step.  The crop is the PatchSize (square,
+a multiple of 16); the option turns dataset.NeedNeighborGT on, so recorded clips deliver the neighbours of every latent frame, and
+synthetic batches get two further seeded frames.  The log line shows this rank's `loss_d` (TensorBoard: `train_loss_d/train`),
+read only at log steps, and checkpoints gain a key `gan` (discriminator and Adamax states) that --resume restores and --reset
+does not; without the term checkpoints are what they were.  Off (W = 0) by default.
 Two things the reference trains without, both off by default: `trainer.clip_grad: {max_norm, norm_type}` / `--clip-grad-norm X` clips
 every optimiser step's gradient by its total norm (norm_type 2 or inf) inside the update's launch -- the log line then shows
 grad_norm, the TensorBoard log `grad_norm/total` and `grad_norm/clip_coef` -- and `trainer.ema: {decay, warmup, validate}` /
@@ -163,6 +170,50 @@ def perceptual_term(net, lin_path, backbone_path, weight, device):
     return PerceptualTerm(model, weight), " (with %g x lpips_%s)" % (weight, net)
 
 
+def adversarial_settings(config, args):
+    """(weight, gan_type) of the STGAN adversarial term (the reference's 'GAN': Adversarial(PatchSize=<crop>, gan_type='STGAN'),
+    train_ours.py:767): --gan_weight, else trainer.gan.weight, else 0 = off; the type is trainer.gan.type, 'STGAN' by default and
+    the only one implemented.  With the term on the crop (trainer.height x trainer.width) is the discriminator's PatchSize: square
+    and a multiple of 16.  Anything else ends the run before any device work."""
+    tr = config.get("trainer", {}) or {}
+    gan = tr.get("gan") or {}
+    flag = getattr(args, "gan_weight", None)
+    weight = float(gan.get("weight", 0.0) if flag is None else flag)
+    gan_type = str(gan.get("type", "STGAN"))
+    if weight < 0:
+        raise SystemExit("train_ours.py: --gan_weight / trainer.gan.weight must not be negative, got %g" % weight)
+    if weight > 0:
+        from ebfi_amd.gan import GAN_TYPES
+        if gan_type not in GAN_TYPES:
+            raise SystemExit("train_ours.py: trainer.gan.type must be one of %s, got %r" % (", ".join(GAN_TYPES), gan_type))
+        H, W = int(tr.get("height", 256)), int(tr.get("width", 256))
+        if H != W or H % 16:
+            raise SystemExit("train_ours.py: the adversarial term needs a square crop whose side is a multiple of 16 (the "
+                             "discriminator's PatchSize), got %d x %d" % (H, W))
+    return weight, gan_type
+
+
+def adversarial_term(patch, gan_type, weight, seed):
+    """-> (AdversarialTerm, the log line's note).  The discriminator is initialised from `seed`, identically on every rank."""
+    from ebfi_amd.gan import Adversarial, AdversarialTerm
+    state = torch.random.get_rng_state()
+    torch.manual_seed(int(seed) + 4099)
+    try:
+        adv = Adversarial(patch, gan_type)
+    finally:
+        torch.random.set_rng_state(state)                  # (the model's initialisation draws what it drew without the term)
+    return AdversarialTerm(adv, weight), " (with %g x %s)" % (weight, gan_type)
+
+
+def with_neighbours(batch, seed, on_device):
+    """A synthetic batch plus two further seeded frames per sample as the neighbours [B, 2, 3, H, W]."""
+    target = batch[4]
+    dev = target.device if on_device else torch.device("cpu")
+    g = torch.Generator(device=dev).manual_seed(int(seed) + 31337)
+    nb = torch.rand((target.shape[0], 2) + tuple(target.shape[1:]), generator=g, device=dev)
+    return tuple(batch) + (nb.to(target.device),)
+
+
 def averaging_settings(config, args=None):
     """{"clip_grad": (max_norm, norm_type) | None, "ema": (decay, warmup) | None, "ema_validate": bool} from trainer.clip_grad
     {max_norm, norm_type = 2} and trainer.ema {decay, warmup = false, validate = true}; --clip-grad-norm X and --ema-decay D
@@ -272,6 +323,8 @@ def checkpoint_state(eng, scheduler, config, iteration, monitor_best=None):
     sched_name = (config.get("lr_scheduler") or {}).get("name")
     ema = eng.ema_state() if getattr(eng, "has_ema", False) else None
     extra = {} if ema is None else {"ema": ema}       # (a sixth key only when the run keeps an average: model.states stays raw)
+    if getattr(eng, "adversarial", None) is not None:   # (likewise `gan`, only with the adversarial term on: the discriminator's
+        extra["gan"] = eng.adversarial.checkpoint_state()   # states and its Adamax states in torch's per-parameter layout)
     return dict({"model": {"name": config["model"]["name"], "states": eng.model.state_dict()},
             "lr_scheduler": {"name": sched_name, "states": scheduler.state_dict() if scheduler is not None else {}},
             "optimizer": {"name": config["optimizer"]["name"], "states": eng.optimizer.state_dict()},
@@ -294,7 +347,8 @@ def resume_checkpoint(path, eng, scheduler, config, reset=False, map_location="c
     """Resumer + _resume_checkpoint of the reference (myutils/utils.py:178-215, train_ours.py:673-716): optimiser and
     scheduler states are restored only without --reset and when the training mode matches, each only when the configured
     name equals the checkpoint's; the model is always loaded (strict=False) when its name matches.  monitor: a Monitor whose
-    `best` is restored from trainer.monitor_best under the same condition as the optimiser state (:696; a checkpoint written
+    `best` is restored from trainer.monitor_best under the same condition as the optimiser state, and so is the discriminator of
+    an engine with the adversarial term from the checkpoint's `gan` entry (:696; a checkpoint written
     without validation carries None and leaves it alone); its not_improved_count restarts at 0.  An engine that keeps a moving
     average of the weights takes it from the checkpoint's `ema` entry under that condition too; with --reset, another training
     mode or a checkpoint without the entry the average starts from the loaded weights.  Returns the first iteration to run."""
@@ -302,6 +356,9 @@ def resume_checkpoint(path, eng, scheduler, config, reset=False, map_location="c
     start = 0
     ema = None
     tr = cpt["trainer"]
+    if not reset and tr.get("training_mode") == TRAINING_MODE and getattr(eng, "adversarial", None) is not None \
+            and cpt.get("gan") is not None:
+        eng.adversarial.load_checkpoint_state(cpt["gan"])    # (--reset, or a checkpoint without the key: a fresh discriminator)
     if not reset and tr.get("training_mode") == TRAINING_MODE:
         if config["optimizer"]["name"] == cpt["optimizer"]["name"]:
             eng.optimizer.load_state_dict(cpt["optimizer"]["states"])
@@ -480,6 +537,13 @@ def train_loop(eng, next_micro_batch, samples_per_pass, unit, st, vs, scheduler,
             if norm is not None:
                 shown = telemetry.last_grad_norm[0] if telemetry is not None and telemetry.last_grad_norm else float(norm[0])
                 norm_note = " grad_norm: %.4e" % shown
+            # with the adversarial term: this rank's discriminator loss of the iteration's last pass, read here only
+            adv = getattr(eng, "adversarial", None)
+            if adv is not None:
+                loss_d = float(adv.loss_d)
+                norm_note += " loss_d: %.4e" % loss_d
+                if telemetry is not None:
+                    telemetry.scalar("train_loss_d/train", loss_d, it)
             print("Iteration: %d/%d train_loss: %.4e%s%s learning rate: %.4e  %.1f %s/s"
                   % (it, st["iterations"], loss.item(), loss_note, norm_note, lr_now, rate, unit), flush=True)
         if t0 is None and eng.settled:
@@ -553,6 +617,10 @@ def get_args(argv=None):
                     help="add W x LPIPS (v0.1; the reference's perceptual_loss) of the restored frame to the "
                          "training loss, differentiated on the device (default: trainer.lpips_weight of the config, else 0 = off); "
                          "needs --lpips_lin and --lpips_backbone")
+    ap.add_argument("--gan_weight", type=float, default=None,
+                    help="add W x the generator's loss of the STGAN adversarial term (the reference's 'GAN': Adversarial(PatchSize="
+                         "crop, gan_type='STGAN')) to the training loss; a patch discriminator is trained beside the model by its own "
+                         "Adamax (default: trainer.gan.weight of the config, else 0 = off)")
     ap.add_argument("--lpips_net", type=str, default=None,
                     help="LPIPS: the trunk, vgg or alex (default: trainer.lpips_net of the config, else vgg; the reference "
                          "trains with alex)")
@@ -574,6 +642,7 @@ def main(argv=None):
         config = yaml.safe_load(fh)
     lpips_net = perceptual_net(config, args)                                          # (refuses before any device work)
     lpips_weight, lpips_lin, lpips_backbone = perceptual_settings(config, args)      # (likewise)
+    gan_weight, gan_type = adversarial_settings(config, args)                         # (likewise)
     optimizer = optimizer_settings(config, args)                                      # (likewise)
     averaging = averaging_settings(config, args)                                      # (likewise)
     tr = config.get("trainer", {}) or {}
@@ -587,11 +656,19 @@ def main(argv=None):
     perceptual, loss_note = None, ""
     if lpips_weight > 0:
         perceptual, loss_note = perceptual_term(lpips_net, lpips_lin, lpips_backbone, lpips_weight, device)
+    adversarial = None
+    if gan_weight > 0:
+        adversarial, gan_note = adversarial_term(int(tr.get("height", 256)), gan_type, gan_weight, args.seed)
+        loss_note += gan_note
+        # the neighbours of every latent frame come with the recorded clips' batches (clipdata, dataset.NeedNeighborGT)
+        loader_cfg = config.get("train_dataloader") or {}
+        loader_cfg["dataset"] = dict(loader_cfg.get("dataset") or {}, NeedNeighborGT=True)
+        config["train_dataloader"] = loader_cfg
     eng = Engine(config["model"]["args"], device=device, precision=args.precision, optimizer=optimizer,
                  seed=args.seed,                                                      # same init on every rank
                  graph=args.graph or bool(tr.get("graph", False)), accu_step=st["accu_step"],
                  backward_f16=False if args.no_f16_backward else None, forward_f16=None if args.no_f16_forward else "filters",
-                 perceptual=perceptual, clip_grad=averaging["clip_grad"], ema=averaging["ema"])
+                 perceptual=perceptual, clip_grad=averaging["clip_grad"], ema=averaging["ema"], adversarial=adversarial)
     scheduler = build_lr_scheduler(config, eng.optimizer.inner)
     # monitor / best checkpoint / early stop (train_ours.py:155-163): only with validation on -- otherwise monitor_best stays None
     monitor = Monitor(vs["monitor"], vs["early_stop"],
@@ -617,8 +694,10 @@ def main(argv=None):
             return next(real)
         # one fresh synthetic batch per pass, different on every rank (seed + rank, like the reference); drawn by the
         # device generator unless --host-data: the host draw alone would cap the loop at ~15 frames/s
-        return make(B, H, W, TB, device=device, seed=args.seed + 1000 * (it * st["accu_step"] + micro), rank=rank,
-                    on_device=not args.host_data)
+        batch_seed = args.seed + 1000 * (it * st["accu_step"] + micro)
+        batch = make(B, H, W, TB, device=device, seed=batch_seed, rank=rank, on_device=not args.host_data)
+        # (with the adversarial term: two further seeded frames per sample as the neighbours)
+        return batch if adversarial is None else with_neighbours(batch, batch_seed + rank, not args.host_data)
 
     telemetry = build_monitor(config, args, args.runid, rank, eng)
     it = train_loop(eng, next_micro_batch, B, "frames", st, vs, scheduler, monitor, valid_batches, tracker, out_dir, config, rank,

@@ -63,6 +63,10 @@
  *   ebfi_charbonnier_*          CharbonnierLoss of the validation loop (loss/restore.py:95-105, train_ours.py:588)
  *   ebfi_duty_head_*            tail of ExposureDecision.forward + nn.MSELoss of stage 1 (model_singleframe.py:75-76,
  *                               train_ours_exposuredecision.py:250-252)
+ *   ebfi_bn_lrelu_* / ebfi_stgan_temporal_* / ebfi_linear_* / ebfi_bce_logits_pair / ebfi_adamax_step
+ *                               Adversarial(gan_type='STGAN') of the training loss dictionary (train_ours.py:767,
+ *                               loss/adversarial.py, loss/discriminator.py:208-263): BatchNorm2d + LeakyReLU in training mode,
+ *                               the temporal input, F.binary_cross_entropy_with_logits and torch.optim.Adamax
  */
 #ifndef EBFI_HIP_H
 #define EBFI_HIP_H
@@ -120,7 +124,10 @@ extern "C" {
  *      DCNv2 package), likewise; and ebfi_grad_norm_workspace / ebfi_grad_norm / ebfi_optim_step_ex (gradient clipping by
  *      total norm and an exponential moving average of the weights around the optimiser step), likewise; and
  *      ebfi_lpips_alex_grad_params_bytes / _pack_grad_params / _train_workspace / _forward_train / _backward (evaluation LPIPS
- *      with the AlexNet trunk as a training loss), likewise */
+ *      with the AlexNet trunk as a training loss), likewise; and ebfi_bn_lrelu_workspace / _forward / _backward,
+ *      ebfi_stgan_temporal_forward / _backward, ebfi_linear_forward / _backward_data / _backward_weight, ebfi_bce_logits_pair
+ *      and ebfi_adamax_step (the STGAN adversarial loss: what
+ *      lies between the discriminator's convolutions, and its Adamax), likewise */
 #define EBFI_ABI_VERSION 14
 
 typedef enum {
@@ -1235,6 +1242,96 @@ int ebfi_flow_max_magnitude(const float *flow, int H, int W, float *out, void *s
 int ebfi_slomo_assemble(const float *I0, const float *I1, const float *flow, double t, float *out20, int H, int W, void *stream);
 int ebfi_slomo_blend(const float *intrp, const float *x20, double t, float *rgb, uint8_t *gray, int H, int W, void *stream);
 int ebfi_slomo_frame_u8(const float *frame, uint8_t *gray, int H, int W, void *stream);
+
+/* ------------------------------------------------------------------ STGAN adversarial loss
+ * 'GAN': Adversarial(PatchSize, gan_type='STGAN') of the reference's loss dictionary (train_ours.py:757-767,
+ * loss/adversarial.py:68-168 over loss/discriminator.py:5-16, 208-263): a spatio-temporal patch discriminator D trained beside
+ * the model by its own Adamax.  What is declared here is everything between D's convolutions (csrc/stgan.hip); the sixteen
+ * convolutions are ebfi_conv2d_forward / _backward_data / _backward_weight* with EBFI_F32, called directly (ebfi_amd.gan).  tests/stgan_ref.py restates the law below in float64.
+ *
+ * The law.  block(ci, co, s) is, in order,
+ *   Conv2d(ci, co, 3, stride = s, padding = 1, bias = False)
+ *   BatchNorm2d(co): eps 1e-5, momentum 0.1, affine, ALWAYS batch statistics: per channel, mean and biased variance over the
+ *     n = B H W values; running_mean <- 0.9 rm + 0.1 mean; running_var <- 0.9 rv + 0.1 var n / (n - 1);
+ *     num_batches_tracked += 1
+ *   LeakyReLU(0.2).
+ * A branch with c input channels is block(c,8,1), (8,8,2), (8,16,1), (16,16,2), (16,32,1), (32,32,2), (32,64,1), (64,64,2).
+ * s_features is a branch with c = 3 on f1; t_features a branch with c = 6 on cat([f1 - f0, f1 - f2], 1).  With q = P / 16 the
+ * classifier flattens the s features to [B, 64 q^2], the t features likewise, concatenates them (s first) and applies
+ * Linear(128 q^2, 1024), LeakyReLU(0.2), Linear(1024, 1): D(f0, f1, f2) is [B, 1].  P % 16 == 0 and H == W == P are required
+ * (ValueError in Python, no device work); a stage with n == 1 (P = 16 at B = 1) is refused, as torch refuses it.
+ * Adversarial(PatchSize, gan_type).forward(fake, real, input_frames) with f0, f2 = input_frames[:, 0], input_frames[:, 1]:
+ *   1. d_fake = D(f0, fake.detach(), f2), then d_real = D(f0, real, f2): two passes, each with its own batch statistics; the
+ *      running statistics are updated in that order.
+ *   2. loss_d = mean(softplus(d_fake)) + mean(softplus(-d_real)), softplus in the stable form of BCE with logits:
+ *      max(x, 0) - x y + log1p(exp(-|x|)) with target y.
+ *   3. the gradients of D's parameters from zero, then ONE Adamax step as torch.optim.Adamax (lr 1e-3, betas (0.9, 0.999),
+ *      eps 1e-8, weight_decay 0): exp_avg <- exp_avg + (1 - b1)(g - exp_avg); exp_inf <- max(b2 exp_inf, |g| + eps);
+ *      p <- p - lr / (1 - b1^t) exp_avg / exp_inf.
+ *   4. d_g = D(f0, fake, f2) with the UPDATED weights (a third running-statistics update); loss_g = mean(softplus(-d_g)) is
+ *      returned with a graph into `fake` only.  (The reference also computes this pass's parameter gradients and zeroes them
+ *      at the next call; they are not computed here.)
+ *   5. self.loss is loss_d (gan_k = 1), kept as a device scalar.
+ * Every other gan_type is refused (NotImplementedError) before any device work.
+ *
+ * Launch contract of every entry point of this section, as of ebfi_lpips_*_train: on `stream` only; no allocation, no host
+ * synchronisation, no floating-point atomics -- the work split of every reduction depends on the shapes only, so two calls on
+ * the same data give the same bits -- and an argument error touches no GPU.  Contiguous float32 tensors.
+ *
+ * ebfi_bn_lrelu_forward: x [B, C, HW] -> y = LeakyReLU_slope(gamma (x - mean) rstd + beta), per-channel mean and biased
+ *   variance of the batch by a two-stage reduction in float64 (chunks of EBFI_BN_CHUNK values of a channel, one float64 pair
+ *   each in the workspace, folded in a fixed order); stats float64 [C, 2] = (mean, rstd = 1 / sqrt(var + eps)) is what the
+ *   backward reads; x - mean is taken in float64, so a plane with mean 100 and spread 0.1 keeps its variance and its
+ *   normalised values.  running_mean / running_var float32 [C] (both or neither; NULL: not kept) and num_batches_tracked (one
+ *   int64, may be NULL) are updated by the same call as written above.
+ * ebfi_bn_lrelu_backward: with dy' = grad_y * (y > 0 ? 1 : slope) and xhat = (x - mean) rstd, the two per-channel sums
+ *   s1 = sum dy', s2 = sum dy' xhat by the same reduction, then grad_x = gamma rstd (dy' - s1 / n - xhat s2 / n),
+ *   grad_gamma = s2, grad_beta = s1 (float32 [C]; either may be NULL -- the generator's pass skips both).  x is the
+ *   convolution's output, y what the forward wrote.
+ * Both: 16-byte accesses when HW % 4 == 0 and the tensors are 16-byte aligned, scalar ones otherwise.  workspace:
+ *   ebfi_bn_lrelu_workspace(B, C, HW) bytes (host arithmetic), 8-byte aligned, overwritten by every call.  Null pointers,
+ *   sizes < 1, B HW == 1 -> EBFI_ERR_ARG; a missing / short workspace -> EBFI_ERR_WORKSPACE; C > 65535 or a grid beyond
+ *   2^31 - 1 -> EBFI_ERR_UNSUPPORTED.
+ * ebfi_stgan_temporal_forward: out [B, 2, CHW] = (f1 - f0, f1 - f2), each input with its own per-sample stride in elements
+ *   (input_frames[:, k] is a strided view); ebfi_stgan_temporal_backward: the adjoint into f1 only,
+ *   grad_f1 [B, CHW] = grad_t[:, 0] + grad_t[:, 1] (+ grad_s, the s branch's gradient, when not NULL), added left to right.
+ * ebfi_linear_forward: y [B, N] = act(x [B, K] weight [N, K]^T + bias) (bias may be NULL; act 0 none, 1 LeakyReLU(slope)), one
+ *   workgroup per output column and eight batch rows: float32 fma sums, a lane its quads of k in order, then a fixed tree.
+ *   ebfi_linear_backward_data: grad_x [B, K] = grad_y [B, N] weight, times LeakyReLU'(mask_y) when mask_y [B, K] (the layer
+ *   below's output) is not NULL; ebfi_linear_backward_weight: grad_weight [N, K] = grad_y^T x and grad_bias [N] (may be NULL),
+ *   summed over the batch in order.  The classifier's two layers are skinny products (B rows against up to 1024 x 32768
+ *   weights, read once per eight rows); they are native so that every sum has one owner and a fixed order -- a captured step
+ *   replays the bits of an eager one, which the BLAS behind torch.nn.functional.linear did not do here.
+ *   B <= 524280, N <= 65535, K < 2^31, else EBFI_ERR_UNSUPPORTED.
+ * ebfi_bce_logits_pair: loss[0] = mean softplus(fake) + mean softplus(-real) over n logits each (float64 sums, one
+ *   workgroup, fixed order); a NULL side contributes nothing (loss_g = the call with fake NULL and real = d_g);
+ *   grad_fake = sigmoid(fake) / n, grad_real = (sigmoid(real) - 1) / n (either may be NULL).
+ * ebfi_adamax_step: the update of step 3 over one flat buffer of n elements, in place, in torch's float32 operations;
+ *   weight_decay != 0: g' = g + weight_decay p first.  grad2 (may be NULL): a second gradient buffer added to the first in
+ *   registers (the fake and the real pass leave one each), neither is written.  step: a device float holding the ALREADY
+ *   incremented count; the bias correction is taken in double.  Hyper-parameters travel by value.  All buffers 16-byte
+ *   aligned; the n % 4 last elements by scalar accesses. */
+#define EBFI_BN_CHUNK 4096
+int64_t ebfi_bn_lrelu_workspace(int64_t B, int C, int64_t HW);
+int ebfi_bn_lrelu_forward(const float *x, const float *gamma, const float *beta, float *y, double *stats, float *running_mean,
+                          float *running_var, int64_t *num_batches_tracked, int64_t B, int C, int64_t HW, double eps,
+                          double momentum, double slope, void *workspace, int64_t workspace_bytes, void *stream);
+int ebfi_bn_lrelu_backward(const float *grad_y, const float *x, const float *y, const float *gamma, const double *stats,
+                           float *grad_x, float *grad_gamma, float *grad_beta, int64_t B, int C, int64_t HW, double slope,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+int ebfi_stgan_temporal_forward(const float *f0, int64_t f0_stride, const float *f1, int64_t f1_stride, const float *f2,
+                                int64_t f2_stride, float *out, int64_t B, int64_t CHW, void *stream);
+int ebfi_stgan_temporal_backward(const float *grad_t, const float *grad_s, float *grad_f1, int64_t B, int64_t CHW, void *stream);
+int ebfi_linear_forward(const float *x, const float *weight, const float *bias, float *y, int64_t B, int64_t K, int64_t N, int act,
+                        double slope, void *stream);
+int ebfi_linear_backward_data(const float *grad_y, const float *weight, const float *mask_y, double slope, float *grad_x, int64_t B,
+                              int64_t K, int64_t N, void *stream);
+int ebfi_linear_backward_weight(const float *grad_y, const float *x, float *grad_weight, float *grad_bias, int64_t B, int64_t K,
+                                int64_t N, void *stream);
+int ebfi_bce_logits_pair(const float *fake, const float *real, int64_t n, float *loss, float *grad_fake, float *grad_real,
+                         void *stream);
+int ebfi_adamax_step(float *param, const float *grad, const float *grad2, float *exp_avg, float *exp_inf, const float *step,
+                     int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
