@@ -42,6 +42,9 @@
  *   ebfi_grad_gather            gradient bucket packing of DistributedDataParallel (train_ours.py:754) as one launch
  *   ebfi_gather_sum             weight re-layouts of the depth-2 Conv3d / ConvTranspose3d (models/model_misc/resnet_3D.py)
  *   ebfi_events_to_stack        dataloader/encodings.py:307-350 (events_to_stack)
+ *   ebfi_events_to_grid / ebfi_interpolate_to_image / ebfi_hot_event_mask / ebfi_stack_to_cnt / ebfi_polarity_mask
+ *                               the rest of dataloader/encodings.py: voxel grids, images, stacks, channels, masks (:8-74, :102-150,
+ *                               :204-304, :353-430) as ordered fp32 sums
  *   ebfi_frame2lap / _frame2dcp myutils/utils.py:34-49 / :15-31
  *   ebfi_frames_u8_to_planar    GetFrames of the real-data reader (dataloader/h5dataset_realdata.py:178-189) + AugmentData's crop / flips
  *   ebfi_planar_to_u8           the uint8 image cast of the evaluation loop (infer_ours.py:135)
@@ -1332,6 +1335,79 @@ int ebfi_bce_logits_pair(const float *fake, const float *real, int64_t n, float 
                          void *stream);
 int ebfi_adamax_step(float *param, const float *grad, const float *grad2, float *exp_avg, float *exp_inf, const float *step,
                      int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay, void *stream);
+
+/* ------------------------------------------------------------------ the rest of dataloader/encodings.py: ordered scatters
+ * ebfi_events_to_grid: an event list (xs, ys, ts, ps: float32 [n] on the device; ts sorted ascending where a mode reads it) ->
+ * out float32 [planes, oH, oW], every element written.  The reference builds all of these with index_put_(accumulate=True) of
+ * fractional weights; THE LAW is what that call computes with one thread (or under torch.use_deterministic_algorithms): every
+ * pixel receives its addends in EVENT-LIST ORDER, each product and sum rounded to fp32, nothing fused, denormals kept.  The
+ * library reaches it without a float atomic: a stable radix sort of (pixel key, event index) with integer histograms, integer
+ * scans and ballot ranks (csrc/encodings.hip), then one thread per (pixel, plane) that walks its pixel's run in ascending event
+ * index.  Two calls on the same input give the same bits; a pixel that owns every event costs the sort nothing extra and the
+ * accumulation one serial walk per plane.  The index is built once per call and serves all planes.
+ * Out-of-range events (x < 0, x >= W, y < 0, y >= H; a NaN coordinate counts as out of range) follow what the reference's
+ * IN-PLACE zeroing (xs = ys = 0 and the weight it was handed = 0) does to its own later passes.  The caller's arrays are never
+ * written; the effect on the output is reproduced per mode (`bins` = planes unless stated):
+ *   EBFI_GRID_IMAGE             events_to_image / events_to_image_torch(interpolation=None); bins = 1.  out[y][x] += p, truncated
+ *                               coordinates; an out-of-range event adds 0 at (0,0).
+ *   EBFI_GRID_VOXEL_BILINEAR    events_to_voxel_torch(temporal_bilinear=True): dt = ts[n-1] - ts[0] + 1e-6f,
+ *                               t = (ts - ts[0]) / dt * (bins - 1), plane b adds p * max(0, 1 - |t - b|).  The weights are a
+ *                               fresh tensor per bin but xs / ys are the caller's: rule 1 -- an out-of-range event adds nothing
+ *                               in bin 0 and its FULL weight at pixel (0,0) in every later bin.  n <= 3 or all stamps zero
+ *                               (sorted non-negative stamps: ts[0] == ts[n-1] == 0, decided on the device) -> zeros.
+ *   EBFI_GRID_VOXEL_NORMALISED  events_to_voxel: stamps already in [0, 1], t = ts * (bins - 1); rule 1 again; no n <= 3 exit.
+ *   EBFI_GRID_VOXEL_NAIVE       events_to_voxel_torch(temporal_bilinear=False) and
+ *   EBFI_GRID_STACK_NO_POLARITY events_to_stack_no_polarity (one law): plane b adds p for the events of the slice [beg, end)
+ *                               that the reference's fp32 bin edges and its own binary search give (end = r + 1: neighbouring
+ *                               bins share edge events).  ps[beg:end] is a view: rule 2 -- the first bin that holds an
+ *                               out-of-range event zeroes its polarity for good, so it adds 0 in every bin.  Same zero exits.
+ *   EBFI_GRID_CHANNELS          events_to_channels; bins = 2.  Plane 0 adds p * (p < 0 ? 0 : p), plane 1 adds p * (p > 0 ? 0 : p).
+ *                               The products are temporaries, the coordinates are not: rule 3 -- the positive pass drops an
+ *                               out-of-range event and moves it, the negative pass counts it at (0,0) (events_to_stack's quirk).
+ *   EBFI_GRID_MASK              events_to_mask; bins = 1.  index_put_(accumulate=False) with duplicates: rule 4 -- the LAST
+ *                               event of a pixel wins, |p|; an out-of-range last writer stores 0 at (0,0).
+ *   EBFI_GRID_BILINEAR_PADDED   events_to_image_torch(interpolation='bilinear', padding=True): out [H+1, W+1]; bins = 1
+ *   EBFI_GRID_BILINEAR_CLIPPED  (..., padding=False, clip_out_of_range=True): out [H, W]; events with x >= W - 1 or y >= H - 1
+ *                               are masked to weight 0 at (0,0).  Both: px = floor(x), dx = x - px, four index_put_ in turn, so a
+ *                               pixel's sum is every top-left addend (w * (1 - dx)) * (1 - dy) in event order, then the
+ *                               top-right (w * dx) * (1 - dy), bottom-left (w * (1 - dx)) * dy and bottom-right (w * dx) * dy ones.
+ *                               (padding=False without clipping raises IndexError in the reference: there is no mode for it.)
+ * ebfi_interpolate_to_image: the same four-pass law IN PLACE on img float32 [H, W] (its old value first), base pixels
+ * pxs / pys int64, fractions and weights float32.  An event whose 2 x 2 footprint leaves the image is skipped (the reference
+ * raises IndexError or, for negative indices, wraps).
+ * workspace: ebfi_events_grid_workspace(n, bins, H, W) bytes for both (host arithmetic; 0 for bad or unsupported sizes; with
+ * bins = 1 and the image's H, W for ebfi_interpolate_to_image), 16-byte aligned, overwritten by every call.  Per call: the key
+ * kernel, four launches per 8 key bits, the run starts, (the bin edges,) the accumulation -- all on `stream`, one chain, no
+ * allocation, nothing read back: capturable.
+ * Null pointers, n < 0, bins / H / W < 1, an unknown mode, bins that contradict the mode, a misaligned workspace -> EBFI_ERR_ARG;
+ * a missing or short workspace -> EBFI_ERR_WORKSPACE; n > 2^31 - 257, (H+1) * (W+1) > 2^31 - 2 or bins > 65535 ->
+ * EBFI_ERR_UNSUPPORTED; none of them touches the GPU.  n == 0 gives zeros (ebfi_interpolate_to_image: a no-op). */
+enum {
+    EBFI_GRID_IMAGE = 0,
+    EBFI_GRID_VOXEL_BILINEAR = 1,
+    EBFI_GRID_VOXEL_NORMALISED = 2,
+    EBFI_GRID_VOXEL_NAIVE = 3,
+    EBFI_GRID_STACK_NO_POLARITY = 4,
+    EBFI_GRID_CHANNELS = 5,
+    EBFI_GRID_MASK = 6,
+    EBFI_GRID_BILINEAR_PADDED = 7,
+    EBFI_GRID_BILINEAR_CLIPPED = 8
+};
+int64_t ebfi_events_grid_workspace(int64_t n, int bins, int H, int W);
+int ebfi_events_to_grid(const float *xs, const float *ys, const float *ts, const float *ps, int64_t n, int mode, int bins, int H,
+                        int W, float *out, void *workspace, int64_t workspace_bytes, void *stream);
+int ebfi_interpolate_to_image(const int64_t *pxs, const int64_t *pys, const float *dxs, const float *dys, const float *weights,
+                              int64_t n, int H, int W, float *img, void *workspace, int64_t workspace_bytes, void *stream);
+/* get_hot_event_mask's loop in one launch (one workgroup): mask float32 [H, W] := 1, then up to max_px times "the first flat
+ * index of the maximum of event_rate (a NaN is the maximum, as in torch.argmax); if its value > max_rate, clear it in event_rate
+ * AND in mask, else stop".  event_rate float32 [H, W] is edited in place -- that is the function's purpose.  max_px == 0 only
+ * fills the mask.  Null pointers, H / W < 1, max_px < 0 -> EBFI_ERR_ARG. */
+int ebfi_hot_event_mask(float *event_rate, int H, int W, int max_px, float max_rate, float *mask, void *stream);
+/* stack2cnt: stack float32 [B, TB, plane] -> cnt float32 [B, 2, plane]: r = rintf(value) (half to even); cnt[b][0] sums
+ * (r < 0 ? 0 : r) and cnt[b][1] sums -(r > 0 ? 0 : r) over the bin axis in bin order, fp32. */
+int ebfi_stack_to_cnt(const float *stack, int64_t B, int TB, int64_t plane, float *cnt, void *stream);
+/* events_polarity_mask: out float32 [2, n], row 0 = (p < 0 ? 0 : p), row 1 = -(p > 0 ? 0 : p) (the caller transposes). */
+int ebfi_polarity_mask(const float *ps, int64_t n, float *out, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
