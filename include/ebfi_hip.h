@@ -45,6 +45,8 @@
  *   ebfi_events_to_grid / ebfi_interpolate_to_image / ebfi_hot_event_mask / ebfi_stack_to_cnt / ebfi_polarity_mask
  *                               the rest of dataloader/encodings.py: voxel grids, images, stacks, channels, masks (:8-74, :102-150,
  *                               :204-304, :353-430) as ordered fp32 sums
+ *   ebfi_iwe_*                  myutils/iwe.py (get_interpolation, interpolate, deblur_events, compute_pol_iwe) and loss/flow.py
+ *                               (EventWarping with its gradient into the flow, AveragedIWE) as ordered fp32 sums
  *   ebfi_frame2lap / _frame2dcp myutils/utils.py:34-49 / :15-31
  *   ebfi_frames_u8_to_planar    GetFrames of the real-data reader (dataloader/h5dataset_realdata.py:178-189) + AugmentData's crop / flips
  *   ebfi_planar_to_u8           the uint8 image cast of the evaluation loop (infer_ours.py:135)
@@ -1408,6 +1410,69 @@ int ebfi_hot_event_mask(float *event_rate, int H, int W, int max_px, float max_r
 int ebfi_stack_to_cnt(const float *stack, int64_t B, int TB, int64_t plane, float *cnt, void *stream);
 /* events_polarity_mask: out float32 [2, n], row 0 = (p < 0 ? 0 : p), row 1 = -(p > 0 ? 0 : p) (the caller transposes). */
 int ebfi_polarity_mask(const float *ps, int64_t n, float *out, void *stream);
+
+/* ------------------------------------------------------------------ loss/flow.py and myutils/iwe.py: images of warped events
+ * events float32 [B, N, 4] = (ts, y, x, p) per event (the code's layout; the reference's docstrings say otherwise); flow maps
+ * float32 [B, 2, H, W] given by their four strides in ELEMENTS (channel 1 is the vertical component); masks float32, one value
+ * per event, `mask_stride` elements apart (pol_mask [B, N, 2]: the pointer, the pointer + 1, stride 2).  csrc/iwe.hip.
+ * THE LAW.  The reference builds every image with scatter_add_ along dim 1; with one thread that is a serial walk, so each
+ * pixel receives its addends in ASCENDING LIST POSITION, every product and sum rounded to fp32, nothing fused.  As for
+ * ebfi_events_to_grid: key = b * H * W + idx per list entry, a stable radix sort of (key, position), one thread per pixel
+ * adding its run in order, each plane its own chain (a run of 64 or more: gathered by the wave, summed in lane order).  No
+ * float atomics.
+ * ebfi_iwe_get_interpolation: flow_ev [B, N, 2] = (y, x) flow per event -> idx, weights float32 [B, M] (M = N with round_idx,
+ *   else 4 N: top-left, top-right, bottom-left, bottom-right lists one after the other).  warped = pos + (((tref - ts) * flow)
+ *   * flow_scaling); corners floor(w), floor(w + 1); weight max(0, 1 - |w - corner|) per axis, y times x; round_idx: rintf (half
+ *   to even), weight 1.  A corner with y < 0, y >= H, x < 0 or x >= W gets index 0 and weight 0 (the reference: -0.0 where the
+ *   coordinate was negative); so does a non-finite warped coordinate (the reference's .long() of it is undefined).
+ * ebfi_iwe_interpolate: idx [B, M] float32 or int64 (idx_is_i64), weights [B, M], polarity_mask [B, M] or NULL -> out
+ *   [B, 1, H, W] = the ordered scatter of weights * polarity_mask (its own rounding).  An index outside [0, H * W) is DROPPED
+ *   (the reference raises).  Workspace: ebfi_iwe_workspace(B, ceil(M / 4), H, W).
+ * ebfi_iwe_deblur: deblur_events (planes = 1, out [B, 1, H, W]; mask_a may be NULL, mask_b is not read) and compute_pol_iwe
+ *   (planes = 2, both masks, out [B, 2, H, W]) in one call: the flow is gathered at each event's source pixel y * W + x, the events are warped to tref = 1
+ *   and scattered with one sort for both masks.  An event whose source pixel is outside the image or not integral takes flow 0
+ *   and weight 0 (the reference's gather raises or asserts).
+ * ebfi_iwe_warping_forward: the loss of EventWarping for ONE flow -> *loss (float32 device scalar) and images float32
+ *   [2 (tref = 1, tref = 0)][B][4 (count+, count-, stamp-weighted sum+, sum-)][H * W], kept by the caller for the backward
+ *   call.  One sort per direction serves its four images; stamp weight (w * ts) * mask forward, (w * (1 - ts)) * mask
+ *   backward; loss = sum of (sum / (count + 1e-9f))^2 over both directions and polarities + weight * (sum of
+ *   sqrt(d^2 + 1e-6) over the differences of the flow along both axes), the squares, roots and both reduction stages in
+ *   float64, in a fixed order.  A NaN in the flow reaches the loss through the smoothness term.
+ * ebfi_iwe_source_index: the events sorted by SOURCE pixel into `index` (ebfi_iwe_index_bytes(B, N, H, W) bytes -- B N entries,
+ *   far smaller than the workspace --, 16-byte aligned, caller-owned, read by every backward call on these events: it does
+ *   not depend on the flow).
+ * ebfi_iwe_warping_backward: grad_flow float32 [B, 2, H, W] (contiguous, every element written once) = *grad_out * d loss /
+ *   d flow.  No scatter: one thread per source pixel walks its events in list order, recomputes the corners of both
+ *   directions, reads 2 r (t - r) / (C + 1e-9f) with r = A / (C + 1e-9f) at each corner and polarity, applies the weight's
+ *   derivative (torch's subgradients: abs'(0) = 0, a tie of max(0, a) passes half) and (tref - ts) * flow_scaling, adds
+ *   forward then backward, then the smoothness gradient from up to four neighbours; float64 accumulation.
+ * ebfi_iwe_averaged: AveragedIWE -> out [B, 2, H, W]: rounded warp to tref = 1, per-polarity counts by the ordered scatter,
+ *   each divided, where positive, by the number of distinct source pixels among the feasible events of that pixel and
+ *   polarity (p < 1 is negative; weight 0 means ignored; pol_mask does not enter that number, as in the reference).
+ * Workspace: ebfi_iwe_workspace(B, N, H, W) bytes (host arithmetic; 0 for bad or unsupported sizes), 16-byte aligned,
+ * overwritten by every call; all launches on `stream`, one chain, nothing allocated or read back: capturable.
+ * Null pointers, B < 1, N < 0, H / W < 1, a misaligned workspace -> EBFI_ERR_ARG; a missing or short workspace ->
+ * EBFI_ERR_WORKSPACE; 4 * B * N >= 2^32 or B * H * W >= 2^32 - 1 -> EBFI_ERR_UNSUPPORTED; none touches the GPU. */
+int64_t ebfi_iwe_workspace(int64_t B, int64_t N, int H, int W);
+int64_t ebfi_iwe_index_bytes(int64_t B, int64_t N, int H, int W);
+int ebfi_iwe_get_interpolation(const float *events, const float *flow_ev, int64_t B, int64_t N, float tref, int H, int W,
+                               float flow_scaling, int round_idx, float *idx, float *weights, void *stream);
+int ebfi_iwe_interpolate(const void *idx, int idx_is_i64, const float *weights, const float *polarity_mask, int64_t B, int64_t M,
+                         int H, int W, float *out, void *workspace, int64_t workspace_bytes, void *stream);
+int ebfi_iwe_deblur(const float *flow, int64_t flow_sb, int64_t flow_sc, int64_t flow_sh, int64_t flow_sw, const float *events,
+                    int64_t B, int64_t N, int H, int W, float flow_scaling, int round_idx, int planes, const float *mask_a,
+                    const float *mask_b, int64_t mask_stride, float *out, void *workspace, int64_t workspace_bytes, void *stream);
+int ebfi_iwe_source_index(const float *events, int64_t B, int64_t N, int H, int W, void *index, int64_t index_bytes, void *stream);
+int ebfi_iwe_warping_forward(const float *flow, int64_t flow_sb, int64_t flow_sc, int64_t flow_sh, int64_t flow_sw,
+                             const float *events, const float *pol_mask, int64_t B, int64_t N, int H, int W, float flow_scaling,
+                             double weight, float *images, float *loss, void *workspace, int64_t workspace_bytes, void *stream);
+int ebfi_iwe_warping_backward(const float *flow, int64_t flow_sb, int64_t flow_sc, int64_t flow_sh, int64_t flow_sw,
+                              const float *events, const float *pol_mask, int64_t B, int64_t N, int H, int W, float flow_scaling,
+                              double weight, const float *images, const void *index, int64_t index_bytes, const float *grad_out,
+                              float *grad_flow, void *stream);
+int ebfi_iwe_averaged(const float *flow, int64_t flow_sb, int64_t flow_sc, int64_t flow_sh, int64_t flow_sw, const float *events,
+                      const float *pol_mask, int64_t B, int64_t N, int H, int W, float flow_scaling, float *out, void *workspace,
+                      int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
