@@ -2103,7 +2103,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16(const float *__restric
     const unsigned go_bytes = (unsigned)g.Cout * (unsigned)HWo * 4u, x_bytes = (unsigned)g.Cin * (unsigned)HW * 4u;
 
     float rg[16], ri[2 * NI];
-    float bsum = 0.f;                      // bias: channel (tid & 63), slot quarter (tid >> 6)
+    // bias: this thread's pixel pair of channels grow + 8*it, summed over its tiles FROM THE FP32 VALUES (the bias gradient
+    // multiplies nothing: summing the bf16 images staged for the matrix cores would round every term to 8 bits for no reason)
+    float bacc[8];
+#pragma unroll
+    for (int it = 0; it < 8; ++it) bacc[it] = 0.f;
     auto prefetch = [&](int tile) {
         int t = tile;
         const int tx = t % tiles_x; t /= tiles_x;
@@ -2165,15 +2169,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16(const float *__restric
         __syncthreads();
         commit();
         __syncthreads();
-        prefetch(tile + gridDim.x);
-        if (need_bias && blockIdx.z == 0) {   // 16 of the 64 pixel slots of one channel per thread (bf16-rounded values)
-            const bf16x8 *gq = reinterpret_cast<const bf16x8 *>(sG + (tid & 63) * GP + (tid >> 6) * 16);
-            const bf16x8 u = gq[0], v = gq[1];
-            float s = 0.f;
+        if (need_bias && blockIdx.z == 0) {   // (before the registers are refilled; slots outside the tile / past Cout hold 0)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) s += (float)u[j] + (float)v[j];
-            bsum += s;
+            for (int it = 0; it < 8; ++it) bacc[it] += rg[2 * it] + rg[2 * it + 1];
         }
+        prefetch(tile + gridDim.x);
         // k-step kk = 16 pixel slots: row kk>>1, columns (kk&1)*16 + 8h .. +7
         const __bf16 *ap = sG + (mt * 32 + (lane & 31)) * GP + (lane >> 5) * 8;
         const __bf16 *bp = sB + (lane & 31) * PLANE + (lane >> 5) * 8;
@@ -2208,13 +2208,19 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16(const float *__restric
             }
         }
     }
-    if (need_bias && blockIdx.z == 0) {    // combine the four slot quarters in a fixed order
+    if (need_bias && blockIdx.z == 0) {    // combine the 32 pixel-pair slots of a channel in a fixed order (64 x 33 floats <= sG)
+        static_assert(64 * 33 * 4 <= 64 * GP * 2, "the bias partials fit the grad_out tile");
         __syncthreads();
         float *red = reinterpret_cast<float *>(smemb);
-        red[tid] = bsum;
+#pragma unroll
+        for (int it = 0; it < 8; ++it) red[(grow + 8 * it) * 33 + gp] = bacc[it];
         __syncthreads();
-        if (tid < 64 && co_base + tid < g.Cout)
-            my[wsz + co_base + tid] = (red[tid] + red[tid + 64]) + (red[tid + 128] + red[tid + 192]);
+        if (tid < 64 && co_base + tid < g.Cout) {
+            float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 32; ++j) s[j & 3] += red[tid * 33 + j];
+            my[wsz + co_base + tid] = (s[0] + s[1]) + (s[2] + s[3]);
+        }
     }
 }
 
@@ -3361,7 +3367,9 @@ int conv_backward_data_bf16_impl(const char *who, int x3, const void *grad_outpu
     if (act != ACT_NONE && !saved_output) return fail(EBFI_ERR_ARG, "%s: activation needs saved_output", who);
     const bool k7 = x3 && ksize == 7 && stride == 1 && weight && act == ACT_NONE;
     if (stride != 1 || pad > ksize - 1 || (!k7 && ksize != 1 && ksize != 3))
-        return fail(EBFI_ERR_UNSUPPORTED, "%s: k=%d stride=%d pad=%d", who, ksize, stride, pad);
+        return fail(EBFI_ERR_UNSUPPORTED, "%s: stride 1 and pad <= k-1 only (got s=%d p=%d k=%d; k in {1,3}, split precision also k=7 "
+                    "without activation); at pad == k the caller drops the outer ring of grad_output and passes pad = k-1",
+                    who, stride, pad, ksize);
     ConvGeom f;
     if (int rc = make_geom(f, B, Cin, H, W, Cout, ksize, stride, pad)) return rc;
     if (B == 0) return EBFI_OK;
@@ -3510,7 +3518,8 @@ extern "C" int ebfi_conv2d_backward_data(const void *grad_output, const void *sa
     if (act != ACT_NONE && !saved_output) return fail(EBFI_ERR_ARG, "conv2d_backward_data: activation needs saved_output");
     if (stride != 1 || pad > ksize - 1)
         return fail(EBFI_ERR_UNSUPPORTED, "conv2d_backward_data: stride 1 and pad <= k-1 only (got s=%d p=%d k=%d); strided layers "
-                    "zero-insert grad_output on the host side", stride, pad, ksize);
+                    "zero-insert grad_output on the host side; at pad == k the caller drops the outer ring of grad_output and "
+                    "passes pad = k-1", stride, pad, ksize);
     ConvGeom f;   // geometry of the forward conv, to validate
     if (int rc = make_geom(f, B, Cin, H, W, Cout, ksize, stride, pad)) return rc;
     if (B == 0) return EBFI_OK;

@@ -5,9 +5,14 @@ activation module; here the forward is one fused kernel (`ebfi_conv2d_forward`),
 runs the stride-1 data gradient on the same kernel with the activation derivative folded into its
 staging (`ebfi_conv2d_backward_data`) plus a deterministic weight/bias gradient
 (`ebfi_conv2d_backward_weight`).  Configurations the kernels do not cover (kernel sizes other than
-1/3, dilation, groups, feature maps smaller than one tile) stay on PyTorch-ROCm's conv; that is a
+1/3/7, strides other than 1/2, dilation, groups) stay on PyTorch-ROCm's conv; that is a
 GPU library path, never a CPU fallback.  Feature maps of any size >= 2 pixels take the native kernels (partial tiles are
 masked): MIOpen would otherwise JIT-compile a kernel per small, unusual shape -- minutes on a fresh machine.
+
+Padding: 0 <= pad <= k (`supported`, and make_geom in csrc/conv2d.hip).  The forward and the weight / bias gradient take the
+whole range; the data-gradient entry points take pad <= k-1 and refuse pad == k.  At pad == k the outer ring of output pixels
+sees padding only, so backward hands them the gradient without that ring at pad = k-1 (`_crop_rings`): a layer that
+`supported` admits runs natively in both directions.
 """
 import os
 
@@ -180,6 +185,11 @@ class ConvBiasAct(Function):
                 N.check(rc, "ebfi_conv2d_backward_weight")
             if need_x:
                 gx = torch.empty_like(x)
+                # pad == k: the data-gradient entry points take pad <= k-1 (_crop_rings); from here on `geo` is theirs
+                ring = max(pad - (k - 1), 0)
+                if ring and stride == 1:
+                    gout, y, gpre = (_crop_rings(t, ring) for t in (gout, y, gpre))
+                    geo = geo[:7] + [k - 1]
                 if bf16:
                     ws, need = _bf16_ws(lib, geo, x.device)
                     rc = lib.ebfi_conv2d_backward_data_bf16mma(N.ptr(gout), N.ptr(y), N.ptr(weight), N.ptr(gx), *geo, act,
@@ -211,7 +221,9 @@ class ConvBiasAct(Function):
                     uh, uw = geo[2] + 2 * pad - k + 1, geo[3] + 2 * pad - k + 1
                     up = gout.new_zeros((geo[0], geo[4], uh, uw))
                     up[:, :, ::stride, ::stride][:, :, :gout.shape[2], :gout.shape[3]] = gpre
-                    geo1 = geo[:6] + [1, pad]
+                    if ring:                     # (the zero-inserted map has the dead rings, not grad_output itself)
+                        up = _crop_rings(up, ring)
+                    geo1 = geo[:6] + [1, pad - ring]
                     if k == 7 and _x3_ok(k, 1, geo[1], mode):
                         ws, need = _bf16_ws(lib, geo1, x.device)
                         rc = lib.ebfi_conv2d_backward_data_bf16x3(N.ptr(up), N.ptr(None), N.ptr(weight), N.ptr(gx), *geo1, ACT_NONE,
@@ -221,6 +233,14 @@ class ConvBiasAct(Function):
                                                            N.EBFI_F32, st)
                 N.check(rc, "ebfi_conv2d_backward_data")
         return gx, gw, gb, None, None, None, None, None
+
+
+def _crop_rings(t, ring):
+    """`t` [B, C, H', W'] without its outer `ring` rows / columns, contiguous (None stays None).  A stride-1 convolution with
+    pad = k-1 + ring has `ring` outer rings of output pixels whose windows lie wholly in the padding: they depend on no input
+    pixel, so the data gradient is that of the pad = k-1 convolution on the gradient without them (the weight gradient does
+    not see them either; the bias gradient does).  The data-gradient entry points of csrc/conv2d.hip take pad <= k-1 only."""
+    return None if t is None else t[:, :, ring:t.shape[2] - ring, ring:t.shape[3] - ring].contiguous()
 
 
 def _act_grad(y, act, slope):
@@ -337,6 +357,9 @@ def _site_backward(site, geo, act, slope, x, y, gout, need_x, need_p, unshuffle=
         if need_x:
             src, sy, a = (gpre, None, ACT_NONE) if gpre is not None else (gout, y, act)
             img = gpre is not None and gpre.dtype == torch.float16
+            # (the fp16 data-gradient kernel stages 16-byte quads of its input: a gradient that arrives as an unaligned view takes
+            # the split-precision kernel, as the weight gradient does, instead of failing with EBFI_ERR_UNSUPPORTED)
+            f16_x = f16_x and src.data_ptr() % 16 == 0
             # (the shuffled store is the fp16 data-gradient kernel's: ungrouped, even sizes, the mask 16-byte aligned like the rest)
             native_unshuffle = unshuffle is not None and (img or (f16_x and a == ACT_NONE)) and site.groups == 1 and H % 2 == 0 and \
                 W % 4 == 0 and Cin > 32 and unshuffle[0].is_contiguous() and unshuffle[0].data_ptr() % 16 == 0
@@ -364,6 +387,9 @@ def _site_backward(site, geo, act, slope, x, y, gout, need_x, need_p, unshuffle=
                                                 site.w_slot_ptr(), st)
                 N.check(rc, "ebfi_conv2d_packed_f16 (data gradient)")
             else:
+                ring = max(pad - (ks - 1), 0)            # pad == k: see _crop_rings
+                if ring:
+                    src, sy, geo = _crop_rings(src, ring), _crop_rings(sy, ring), geo[:7] + [ks - 1]
                 rc = lib.ebfi_conv2d_backward_data_bf16x3(N.ptr(src), N.ptr(sy), N.ptr(None), N.ptr(gx), *geo, a,
                                                           slope if a != ACT_NONE else 0.0, site.tr_ptr(), site.tr_bytes, st)
                 N.check(rc, "ebfi_conv2d_backward_data_bf16x3 (packed)")
