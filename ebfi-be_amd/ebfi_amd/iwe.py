@@ -18,7 +18,8 @@ the flow still reaches the loss through the smoothness term.  Unfeasible corners
 store ``-0.0``.
 
 float32 GPU tensors only; float64, CPU tensors, mixed devices, ``4 * B * N >= 2**32`` and ``B * H * W >= 2**32 - 1`` are
-refused.  The caller's tensors are never written.  ``BrightnessConstancy`` (loss/reconstruction.py) is not provided.
+refused.  The caller's tensors are never written.  ``BrightnessConstancy`` (loss/reconstruction.py), the consumer of
+``AveragedIWE``, is in ebfi_amd/bcloss.py.
 """
 import torch
 import torch.nn as nn

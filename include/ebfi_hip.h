@@ -47,6 +47,8 @@
  *                               :204-304, :353-430) as ordered fp32 sums
  *   ebfi_iwe_*                  myutils/iwe.py (get_interpolation, interpolate, deblur_events, compute_pol_iwe) and loss/flow.py
  *                               (EventWarping with its gradient into the flow, AveragedIWE) as ordered fp32 sums
+ *   ebfi_bc_* / ebfi_sobel_*    loss/reconstruction.py (BrightnessConstancy: generative model, temporal consistency, total variation)
+ *                               and myutils/gradients.py (Sobel), each with its gradients; the grid_sample adjoint as an ordered fp32 sum
  *   ebfi_frame2lap / _frame2dcp myutils/utils.py:34-49 / :15-31
  *   ebfi_frames_u8_to_planar    GetFrames of the real-data reader (dataloader/h5dataset_realdata.py:178-189) + AugmentData's crop / flips
  *   ebfi_planar_to_u8           the uint8 image cast of the evaluation loop (infer_ours.py:135)
@@ -1473,6 +1475,68 @@ int ebfi_iwe_warping_backward(const float *flow, int64_t flow_sb, int64_t flow_s
 int ebfi_iwe_averaged(const float *flow, int64_t flow_sb, int64_t flow_sc, int64_t flow_sh, int64_t flow_sw, const float *events,
                       const float *pol_mask, int64_t B, int64_t N, int H, int W, float flow_scaling, float *out, void *workspace,
                       int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ loss/reconstruction.py and myutils/gradients.py
+ * BrightnessConstancy's three terms and the Sobel operator, with their gradients.  csrc/bcloss.hip.  Images are float32,
+ * contiguous, one channel: [B, 1, H, W] (Sobel and the total variation: `planes` images [H, W]); flow maps float32 [B, 2, H, W]
+ * given by their four strides in ELEMENTS (channel 0 horizontal, channel 1 vertical), in units of S = flow_scaling = max(H, W).
+ * THE LAW.  Pixel (h, w) samples at ix = ((gx + 1) * W - 1) / 2 with gx = 2 * (w - fx * S) / (W - 1) - 1, and iy alike with H
+ * (grid_sample without align_corners -- not w - fx * S), bilinear, corners outside the image contribute 0; a coordinate that is
+ * not finite samples 0 and passes no gradient.  The per-pixel arithmetic is float64 of the float32 inputs; every loss is a
+ * float64 sum in two stages of fixed order -> *loss, a float32 device scalar.  The gradient into the flow is a gather; the
+ * gradient into the SAMPLED image is the scatter, as an ordered sum: every destination pixel adds its float32 addends in
+ * ascending source-pixel index, then corner order top-left, top-right, bottom-left, bottom-right, fp32 and unfused -- a stable
+ * radix sort of the 4 B H W (destination, source) entries and one thread per destination, as for ebfi_iwe_* (a run of 64 or
+ * more: gathered by the wave, summed in lane order).  No float atomics.
+ * ebfi_sobel_forward: x [planes, H, W] -> gradx, grady [planes, H, W]: replication pad of one pixel, correlation with
+ *   [[-1,0,1],[-2,0,2],[-1,0,1]] and [[-1,-2,-1],[0,0,0],[1,2,1]], divided by 8.  ebfi_sobel_backward: the adjoint as a
+ *   gather -> grad_x (every element written); either incoming gradient may be NULL, not both.
+ * ebfi_bc_mask_flow: masked [B, 2, H, W] contiguous = flow * m with m = 1 where the channel sum s of cnt [B, C, H, W] (added in
+ *   channel order, fp32) is positive and s itself elsewhere: the flow AveragedIWE reads.  It is the generative term's third
+ *   launch beside the pixel kernel and the final reduction: csrc/iwe.hip is pinned by a host test and takes no mask.
+ * ebfi_bc_generative_forward: with the masked flow f (recomputed per pixel), the Sobel values of the four corners from the
+ *   4 x 4 window of img with clamped coordinates, pred = (Sx fx + Sy fy) * S, resid [B, H, W] = (avg[:, 0] - avg[:, 1]) + pred
+ *   (avg [B, 2, H, W]: AveragedIWE of the masked flow), *loss = sum resid^2.  resid is kept by the caller for
+ * ebfi_bc_generative_backward: grad_flow [B, 2, H, W] contiguous = m * d loss / d f (through the product and through the grid;
+ *   exactly +0 where m == 0) and grad_img [B, 1, H, W] = the ordered scatter into the two Sobel gradient images, then the
+ *   Sobel adjoint.  Either may be NULL (not both); without grad_img nothing is sorted and the forward workspace suffices.
+ *   No gradient through avg.
+ * ebfi_bc_temporal_forward: resid = img - sample(prev_img) under the flow as given, *loss = weight * sum |resid|.
+ * ebfi_bc_temporal_backward: grad_flow, grad_prev (the ordered scatter) and grad_img = weight * *grad_out * sign(resid), sign(0)
+ *   = 0; each may be NULL, not all; the full workspace is needed only with grad_prev.
+ * ebfi_bc_tv_forward / _backward: *loss = weight * (sum |x[h] - x[h + 1]| + sum |x[w] - x[w + 1]|) per image; the gradient is a
+ *   gather from up to four neighbours.
+ * Workspace: ebfi_bc_workspace(B, H, W) bytes for a backward call, ebfi_bc_forward_workspace(B, H, W) (its first part: the
+ * partial sums) for a forward call -- host arithmetic, 0 for bad or unsupported sizes --, 16-byte aligned, overwritten by every
+ * call; all launches on `stream`, one chain, nothing allocated or read back: capturable.
+ * Null pointers, B < 1, C < 1, H < 2 or W < 2 (the law divides by n - 1), a misaligned workspace -> EBFI_ERR_ARG; a missing or
+ * short workspace -> EBFI_ERR_WORKSPACE; 4 * B * H * W >= 2^32 for the entry points of the two sampling terms and
+ * ebfi_bc_mask_flow (entry positions of the sort are 32-bit), planes * H * W >= 2^32 - 1 for Sobel and the total variation, which
+ * sort nothing -> EBFI_ERR_UNSUPPORTED; none touches the GPU. */
+int64_t ebfi_bc_workspace(int64_t B, int H, int W);
+int64_t ebfi_bc_forward_workspace(int64_t B, int H, int W);
+int ebfi_sobel_forward(const float *x, int64_t planes, int H, int W, float *gradx, float *grady, void *stream);
+int ebfi_sobel_backward(const float *grad_gradx, const float *grad_grady, int64_t planes, int H, int W, float *grad_x, void *stream);
+int ebfi_bc_mask_flow(const float *flow, int64_t flow_sb, int64_t flow_sc, int64_t flow_sh, int64_t flow_sw, const float *cnt, int C,
+                      int64_t B, int H, int W, float *masked, void *stream);
+int ebfi_bc_generative_forward(const float *flow, int64_t flow_sb, int64_t flow_sc, int64_t flow_sh, int64_t flow_sw,
+                               const float *img, const float *cnt, int C, const float *avg, int64_t B, int H, int W,
+                               float flow_scaling, float *resid, float *loss, void *workspace, int64_t workspace_bytes, void *stream);
+int ebfi_bc_generative_backward(const float *flow, int64_t flow_sb, int64_t flow_sc, int64_t flow_sh, int64_t flow_sw,
+                                const float *img, const float *cnt, int C, const float *resid, int64_t B, int H, int W,
+                                float flow_scaling, const float *grad_out, float *grad_flow, float *grad_img, void *workspace,
+                                int64_t workspace_bytes, void *stream);
+int ebfi_bc_temporal_forward(const float *flow, int64_t flow_sb, int64_t flow_sc, int64_t flow_sh, int64_t flow_sw,
+                             const float *prev_img, const float *img, int64_t B, int H, int W, float flow_scaling, double weight,
+                             float *resid, float *loss, void *workspace, int64_t workspace_bytes, void *stream);
+int ebfi_bc_temporal_backward(const float *flow, int64_t flow_sb, int64_t flow_sc, int64_t flow_sh, int64_t flow_sw,
+                              const float *prev_img, const float *resid, int64_t B, int H, int W, float flow_scaling, double weight,
+                              const float *grad_out, float *grad_flow, float *grad_prev, float *grad_img, void *workspace,
+                              int64_t workspace_bytes, void *stream);
+int ebfi_bc_tv_forward(const float *img, int64_t planes, int H, int W, double weight, float *loss, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+int ebfi_bc_tv_backward(const float *img, int64_t planes, int H, int W, double weight, const float *grad_out, float *grad_img,
+                        void *stream);
 
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
