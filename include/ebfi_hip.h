@@ -1538,6 +1538,48 @@ int ebfi_bc_tv_forward(const float *img, int64_t planes, int H, int W, double we
 int ebfi_bc_tv_backward(const float *img, int64_t planes, int H, int W, double weight, const float *grad_out, float *grad_img,
                         void *stream);
 
+/* ------------------------------------------------------------------ models/model_misc/unet.py: what lies between the convolutions
+ * The ConvLSTM and ConvGRU cell tails of models/model_misc/submodules.py and UpsampleConvLayer's bilinear up-sampling, each with
+ * its gradient.  csrc/recurrent.hip.  Tensors are float32, contiguous [B, channels, H, W]; HW = H * W.  One launch per call on
+ * `stream`, nothing allocated or read back, NO atomics: capturable and bit-reproducible.  16-byte accesses when HW % 4 == 0 and
+ * every tensor is 16-byte aligned, scalar ones otherwise.  float32, no contraction; with e = expf(-|v|), sigmoid(v) and
+ * 1 - sigmoid(v) are 1 / (1 + e) and e / (1 + e) (swapped for v < 0), and 1 - tanh(v)^2 past |v| = 0.625 is 4 e' / (1 + e')^2,
+ * e' = expf(-2 |v|): no complement is formed by subtracting from 1, so a saturated gate keeps its derivative's accuracy.
+ * ebfi_lstm_cell_forward: gates [B, 4C, HW] are the pre-activations in chunk order in, remember, out, cell; with i, f, o their
+ *   sigmoids and g = tanh(cell gate): cell = f * prev_cell + i * g, hidden = o * tanh(cell).  prev_cell NULL = zeros.
+ * ebfi_lstm_cell_backward: from gates, prev_cell (NULL = zeros), the saved cell and grad_hidden / grad_cell (either NULL = zero)
+ *   -> grad_gates [B, 4C, HW], the gradient of the PRE-activations, and grad_prev_cell (NULL = not wanted).  The sigmoids and
+ *   both tanh are recomputed: d = grad_cell + grad_hidden o (1 - tanh(cell)^2); (d g i (1 - i), d prev_cell f (1 - f),
+ *   grad_hidden tanh(cell) o (1 - o), d i (1 - g^2)); grad_prev_cell = d f.
+ * ebfi_gru_reset_forward: out [B, Cx + C, HW] = cat(x [B, Cx, HW], h * sigmoid(reset_pre)) -- the input of the out-gate
+ *   convolution, written once.  h NULL = zeros (reset_pre is then not read).
+ * ebfi_gru_reset_backward: grad_out [B, Cx + C, HW] -> grad_x = its first Cx channels (NULL = not wanted), grad_reset_pre =
+ *   g h r (1 - r) and grad_h = grad_h_in + g r (g the last C channels, r = sigmoid(reset_pre); grad_h_in, the direct term of
+ *   the second half, may be NULL = zero; grad_h NULL = not wanted).  h NULL: grad_reset_pre and grad_h are zeros.
+ * ebfi_gru_update_forward: new_state = h * (1 - u) + tanh(out_pre) * u with u = sigmoid(update_pre); h NULL = zeros.
+ * ebfi_gru_update_backward: grad_update_pre = g (t - h) u (1 - u), grad_out_pre = g u (1 - t^2), grad_h = g (1 - u) (NULL = not
+ *   wanted), t = tanh(out_pre).
+ * ebfi_bilinear_up_forward: x [planes, H, W] -> out [planes, scale H, scale W], scale 2 or 4, the law of F.interpolate(mode =
+ *   'bilinear', align_corners = False): source coordinate (o + 0.5) / scale - 0.5, a negative one clamped to 0, i0 its integer
+ *   part, i1 = i0 + 1 below n - 1 (else i0), weights 1 - fraction and fraction.
+ * ebfi_bilinear_up_backward: the adjoint as a gather: every input pixel adds (wy * wx) * grad_out over its contributors
+ *   o in [scale i - scale / 2, scale i + 3 scale / 2 - 1] per axis, rows ascending, then columns ascending, in float32.
+ * A null required pointer, B / C / Cx / HW / planes / H / W < 1, a scale other than 2 or 4 -> EBFI_ERR_ARG; nothing is launched. */
+int ebfi_lstm_cell_forward(const float *gates, const float *prev_cell, float *hidden, float *cell, int64_t B, int C, int64_t HW,
+                           void *stream);
+int ebfi_lstm_cell_backward(const float *gates, const float *prev_cell, const float *cell, const float *grad_hidden,
+                            const float *grad_cell, float *grad_gates, float *grad_prev_cell, int64_t B, int C, int64_t HW, void *stream);
+int ebfi_gru_reset_forward(const float *reset_pre, const float *x, const float *h, float *out, int64_t B, int Cx, int C, int64_t HW,
+                           void *stream);
+int ebfi_gru_reset_backward(const float *grad_out, const float *reset_pre, const float *h, const float *grad_h_in, float *grad_x,
+                            float *grad_reset_pre, float *grad_h, int64_t B, int Cx, int C, int64_t HW, void *stream);
+int ebfi_gru_update_forward(const float *update_pre, const float *out_pre, const float *h, float *new_state, int64_t B, int C, int64_t HW,
+                            void *stream);
+int ebfi_gru_update_backward(const float *update_pre, const float *out_pre, const float *h, const float *grad_new, float *grad_update_pre,
+                             float *grad_out_pre, float *grad_h, int64_t B, int C, int64_t HW, void *stream);
+int ebfi_bilinear_up_forward(const float *x, float *out, int64_t planes, int H, int W, int scale, void *stream);
+int ebfi_bilinear_up_backward(const float *grad_out, float *grad_x, int64_t planes, int H, int W, int scale, void *stream);
+
 /* ------------------------------------------------------------------ per-kernel device timing
  * When enabled, every launch made by this library is bracketed by a hipEvent pair recorded on the
  * launch stream.  ebfi_prof_collect() must be called after the stream(s) are synchronised; it
