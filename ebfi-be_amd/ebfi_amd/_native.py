@@ -16,7 +16,7 @@ import threading
 
 PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))      # .../ebfi-be_amd
 REPO_ROOT = os.path.dirname(PKG_ROOT)
-# Development variables (EBFI_LIB_PATH below, EBFI_C16_POISON in ebfi_amd.c16): honoured only in a process started with
+# Development variables (EBFI_LIB_PATH below): honoured only in a process started with
 # EBFI_DEV=1, so that a stray variable cannot change what a production run, one of its ranks or one of its graph captures
 # computes.  No variable selects a kernel: an A/B comparison builds the other tree into a second library (csrc/build.sh with
 # EBFI_LIB_OUT / EBFI_OBJ_DIR) and loads it here, or runs two trees.
