@@ -1289,11 +1289,14 @@ template <int KS, int S, int WTXO = 0>
 struct WCfg {
     // output columns per tile: the staged input row must fit 32 (or 64) lanes; 3x3 stride-1 may pick 26/28/30
     // (WTXO) so that ceil(Wo / WTX) * WTX wastes as few columns as possible (128 -> 26: 1.5 % instead of 15 %)
-    static constexpr int WTX = WTXO ? WTXO : ((KS == 1) ? 32 : (KS == 3) ? 30 : (S == 1 ? 26 : 28));
+    // 5x5: 28 columns at stride 1 (a 32-lane input row), 30 at stride 2 (a 63-column row on 64 lanes)
+    static constexpr int WTX = WTXO ? WTXO : ((KS == 1) ? 32 : (KS == 3) ? 30 : (KS == 5) ? (S == 1 ? 28 : 30) : (S == 1 ? 26 : 28));
     static constexpr int IH = S * (WTY - 1) + KS, IW = S * (WTX - 1) + KS;
     static constexpr int IWP = IW <= 32 ? 32 : 64;              // lanes per staged input row
     static constexpr int TROWS = 256 / IWP;                     // thread rows walking (row, channel)
-    static constexpr int CIB = KS == 7 ? 8 : (S == 2 ? 32 : 64);   // input channels per workgroup
+    // input channels per workgroup (5x5: 16 channels = 400 columns = 7 n-tiles = 112 accumulator registers per wave, beside
+    // 16 + 12 / 28 staging registers at two workgroups per CU)
+    static constexpr int CIB = KS == 7 ? 8 : (KS == 5 ? 16 : (S == 2 ? 32 : 64));
     // LDS image strides with IWS == KS and PS == KS*KS (mod 32): column n = ci*KK + ky*KS + kx of the GEMM then
     // sits in bank n mod 32, so the 32 lanes of a B-operand fetch never collide
     static constexpr int IWS = IW + ((KS - IW) % 32 + 32) % 32;
@@ -2377,10 +2380,11 @@ double conv_bytes_wgrad(const ConvGeom &g, int kk, bool dact, bool side_out) {
                   (double)g.Cout * g.Cin * kk);
 }
 
-// fwd5: the caller is the exact-fp32 forward, the one place a 5x5 (stride 1) kernel exists
-int make_geom(ConvGeom &g, int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad, bool fwd5 = false) {
+// k5: 0 = the caller has no 5x5 kernel; 1 = the exact-fp32 forward of ebfi_conv2d_forward (5x5 at stride 1 only);
+//     2 = the ebfi_conv5x5_* entry points (stride 1 and 2; they check pad <= 4 themselves)
+int make_geom(ConvGeom &g, int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad, int k5 = 0) {
     if (B < 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return fail(EBFI_ERR_ARG, "conv2d: non-positive dimension");
-    if (ks != 1 && ks != 3 && ks != 7 && !(fwd5 && ks == 5 && stride == 1))
+    if (ks != 1 && ks != 3 && ks != 7 && !(ks == 5 && (k5 == 2 || (k5 == 1 && stride == 1))))
         return fail(EBFI_ERR_UNSUPPORTED, "conv2d: kernel size %d (1, 3 and 7 implemented; 5 in the fp32 stride-1 forward)", ks);
     if (stride != 1 && stride != 2) return fail(EBFI_ERR_UNSUPPORTED, "conv2d: stride %d (1 and 2 implemented)", stride);
     if (pad < 0 || pad > ks) return fail(EBFI_ERR_ARG, "conv2d: padding %d out of range", pad);
@@ -2442,6 +2446,7 @@ int wgrad_wtx_rt(const ConvGeom &g, int ks, int stride) {
     if (ks == 3 && stride == 1) return pick_wtx(g.Wo);
     if (ks == 3) return WCfg<3, 2>::WTX;
     if (ks == 1) return WCfg<1, 1>::WTX;
+    if (ks == 5) return stride == 1 ? WCfg<5, 1>::WTX : WCfg<5, 2>::WTX;
     return stride == 1 ? WCfg<7, 1>::WTX : WCfg<7, 2>::WTX;
 }
 
@@ -2449,7 +2454,7 @@ int64_t wgrad_tiles_rt(const ConvGeom &g, int ks, int stride) {
     return (int64_t)g.B * ceil_div(g.Ho, WTY) * ceil_div(g.Wo, wgrad_wtx_rt(g, ks, stride));
 }
 
-int wgrad_cib_rt(int ks, int stride) { return ks == 7 ? 8 : (stride == 2 ? 32 : 64); }
+int wgrad_cib_rt(int ks, int stride) { return ks == 7 ? 8 : (ks == 5 ? WCfg<5, 1>::CIB : (stride == 2 ? 32 : 64)); }
 
 int wgrad_splits(const ConvGeom &g, int ks, int stride, bool bf16mma = false) {
     const int64_t tiles = wgrad_tiles_rt(g, ks, stride);
@@ -2490,6 +2495,8 @@ int launch_wgrad_t(hipStream_t st, const float *x, const float *gout, const floa
 template <int KS, int S>
 int launch_wgrad(hipStream_t st, const float *x, const float *gout, const float *yact, float *slab, float *gpre_out,
                  const ConvGeom &g, int dact, float dslope, int nsplit, int need_bias) {
+    // (5x5 has one tile width: returning here only keeps the <5, S, 26> and <5, S, 28> kernels below from being instantiated)
+    if constexpr (KS == 5) return launch_wgrad_t<KS, S, 0>(st, x, gout, yact, slab, gpre_out, g, dact, dslope, nsplit, need_bias);
     if (KS == 3 && S == 1) {
         const int w = pick_wtx(g.Wo);
         if (w == 26) return launch_wgrad_t<KS, S, 26>(st, x, gout, yact, slab, gpre_out, g, dact, dslope, nsplit, need_bias);
@@ -3392,6 +3399,176 @@ int conv_backward_data_bf16_impl(const char *who, int x3, const void *grad_outpu
         return launch_fwd_bf16<3>(st, go, yo, w, nullptr, gi, g, 1, ACT_NONE, 0.f, act, slope, workspace, workspace_bytes, x3);
     return launch_fwd_bf16<1>(st, go, yo, w, nullptr, gi, g, 1, ACT_NONE, 0.f, act, slope, workspace, workspace_bytes, x3);
 }
+
+// ------------------------------------------------------------------------------------------------
+// conv5s2_dgrad_f32: data gradient of a 5x5 STRIDE-2 convolution in exact fp32, by output parity on the gradient itself
+// (conv7s2_dgrad_x3 is the precedent), for any pad 0..4.  With Y = y + pad = 2u + py input pixel (y, x) receives the taps
+// ky = py, py + 2, (py + 4) from the gradient rows oy = u - (ky >> 1):
+//     gx[ci][y][x] = sum_co sum_{ky = py (2) 4} sum_{kx = px (2) 4} W[co][ci][ky][kx] * g[co][u - (ky >> 1)][v - (kx >> 1)]
+// -- the four classes (py, px) see 3x3, 3x2, 2x3 and 2x2 taps, 25 per (u, v) and channel pair where a zero-inserted map costs
+// 100, and no [B, Cout, H + 2 pad - 4, W + 2 pad - 4] temporary is filled, scattered into and read.
+// GEMM as in conv_fwd_f32: M = 32 gradient (= forward input) channels, N = 4 x 64 positions (u, v), K = forward output
+// channels in chunks of CK.  A workgroup stages the 6 x 66 halo tile of g (times act'(saved output)) and the weight slice
+// [k][tap][m] once per chunk; wave `w` owns row u0 + w and keeps one accumulator pair per class: acc[py][px][n].  Gradient
+// rows / columns outside [0, Ho) x [0, Wo) are staged as zeros, so an input row or column that no window reaches (H + 2 pad - 5
+// odd) is written as zero like every other element of grad_input.
+constexpr int C5S_IH = TY + 2, C5S_IW = TX + 2, C5S_PS = C5S_IH * C5S_IW;
+
+template <int CK, int DACT>
+__global__ __launch_bounds__(256) void conv5s2_dgrad_f32(const float *__restrict__ gout, const float *__restrict__ dact_y,
+                                                         const float *__restrict__ w, float *__restrict__ gx, ConvGeom f,
+                                                         float dslope) {
+    // f: the FORWARD geometry (gout [B, f.Cout, f.Ho, f.Wo], w [f.Cout][f.Cin][5][5], gx [B, f.Cin, f.H, f.W])
+    constexpr int KS = 5, KK = KS * KS, PS = C5S_PS, IW = C5S_IW;
+    constexpr int COS = 32, COSP = COS + 4;
+    constexpr int NPOS = (PS + 255) / 256;
+    constexpr int WEL = KK * CK * COS, NW = (WEL + 255) / 256;
+    __shared__ float sIn[CK * PS];
+    __shared__ float sW[KK * CK * COSP];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ub = f.pad >> 1;                                            // u (and v) of input row (column) 0
+    const int Hu = ((f.H - 1 + f.pad) >> 1) - ub + 1, Wu = ((f.W - 1 + f.pad) >> 1) - ub + 1;
+    const int tiles_x = (Wu + TX - 1) / TX, tiles_y = (Hu + TY - 1) / TY;
+    int t = blockIdx.x;
+    const int tx = t % tiles_x; t /= tiles_x;
+    const int ty = t % tiles_y;
+    const int b = t / tiles_y;
+    const int u0 = ub + ty * TY, v0 = ub + tx * TX;
+    const int m_base = blockIdx.y * COS;
+    const int HWo = f.Ho * f.Wo, HW = f.H * f.W;
+    const unsigned plane_bytes = (unsigned)HWo * 4u, g_bytes = (unsigned)f.Cout * plane_bytes;
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(gout + (int64_t)b * f.Cout * HWo, g_bytes);
+    const __amdgpu_buffer_rsrc_t ry = make_rsrc(DACT ? dact_y + (int64_t)b * f.Cout * HWo : gout, DACT ? g_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t rwt = make_rsrc(w, (unsigned)f.Cout * (unsigned)f.Cin * KK * 4u);
+
+    f32x16 acc[2][2][2];                   // [py][px][n]
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i >> 2][(i >> 1) & 1][i & 1][r] = 0.f;
+
+    unsigned in_off[NPOS];                 // byte offset of the owned tile position inside a gradient plane
+#pragma unroll
+    for (int q = 0; q < NPOS; ++q) {
+        const int pos = tid + q * 256;
+        const int r = pos / IW, c = pos - r * IW;
+        const int yy = u0 - 2 + r, xx = v0 - 2 + c;
+        in_off[q] = (pos < PS && yy >= 0 && yy < f.Ho && xx >= 0 && xx < f.Wo) ? (unsigned)(yy * f.Wo + xx) * 4u : SENT;
+    }
+    unsigned w_off[NW];                    // W[co = k][ci = m][tap] of chunk 0
+    int w_dst[NW];                         // its place in the LDS slice [k][tap][m]
+#pragma unroll
+    for (int it = 0; it < NW; ++it) {
+        const int i = tid + it * 256;
+        const int k = i / (COS * KK), rem = i - k * (COS * KK);
+        const int m = rem / KK, tap = rem - m * KK;
+        w_off[it] = i < WEL ? (unsigned)((k * f.Cin + m_base + m) * KK + tap) * 4u : SENT;
+        w_dst[it] = (k * KK + tap) * COSP + m;
+    }
+    // (rows m >= Cin of the slice may alias other weights: they are never stored; channels k >= Cout read 0 on both sides)
+    const unsigned w_chunk = (unsigned)(CK * f.Cin * KK) * 4u;
+
+    float rin[NPOS * CK], rw[NW];
+    auto prefetch = [&](int chunk) {
+        const unsigned cb = (unsigned)chunk * (unsigned)CK * plane_bytes;
+#pragma unroll
+        for (int q = 0; q < NPOS; ++q)
+#pragma unroll
+            for (int ci = 0; ci < CK; ++ci) {
+                const unsigned o = in_off[q] + cb + (unsigned)ci * plane_bytes;
+                float v = buf_ld(rx, o);
+                if constexpr (DACT != 0) v *= act_grad_c<DACT>(buf_ld(ry, o), dslope);
+                rin[q * CK + ci] = v;
+            }
+        const unsigned wb = (unsigned)chunk * w_chunk;
+#pragma unroll
+        for (int it = 0; it < NW; ++it) rw[it] = buf_ld(rwt, w_off[it] + wb);
+    };
+    auto commit = [&]() {
+#pragma unroll
+        for (int q = 0; q < NPOS; ++q)
+            if (tid + q * 256 < PS) {
+#pragma unroll
+                for (int ci = 0; ci < CK; ++ci) sIn[ci * PS + tid + q * 256] = rin[q * CK + ci];
+            }
+#pragma unroll
+        for (int it = 0; it < NW; ++it)
+            if (tid + it * 256 < WEL) sW[w_dst[it]] = rw[it];
+    };
+
+    const int nchunks = (f.Cout + CK - 1) / CK;
+    prefetch(0);
+    for (int chunk = 0; chunk < nchunks; ++chunk) {
+        __syncthreads();
+        commit();
+        __syncthreads();
+        prefetch(chunk + 1);      // past the last chunk every offset is out of range: reads 0, never committed
+        const float *bp = sIn + (lane >> 5) * PS + (wave + 2) * IW + (lane & 31) + 2;
+        const float *ap = sW + (lane >> 5) * (KK * COSP) + (lane & 31);
+#pragma unroll
+        for (int ky = 0; ky < KS; ++ky) {
+#pragma unroll
+            for (int kx = 0; kx < KS; ++kx) {
+                const int py = ky & 1, px = kx & 1, dy = ky >> 1, dx = kx >> 1;
+#pragma unroll
+                for (int cp = 0; cp < CK; cp += 2) {
+                    const float a = ap[(cp * KK + ky * KS + kx) * COSP];
+#pragma unroll
+                    for (int n = 0; n < 2; ++n)
+                        acc[py][px][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bp[cp * PS - dy * IW - dx + n * 32], acc[py][px][n], 0, 0, 0);
+                }
+            }
+        }
+    }
+    // ---- store: class (py, px) of position (u, v) is input pixel (2u + py - pad, 2v + px - pad); rows m >= Cin and pixels
+    // outside the image fall out of the descriptor's range
+    const int u = u0 + wave, h = lane >> 5, l31 = lane & 31;
+    const unsigned oplane = (unsigned)HW * 4u;
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(gx + (int64_t)b * f.Cin * HW, (unsigned)f.Cin * oplane);
+#pragma unroll
+    for (int py = 0; py < 2; ++py) {
+        const int y = 2 * u + py - f.pad;
+        const bool y_ok = y >= 0 && y < f.H;
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const int v = v0 + n * 32 + l31;
+#pragma unroll
+            for (int px = 0; px < 2; ++px) {
+                const int x = 2 * v + px - f.pad;
+                const unsigned base = (y_ok && x >= 0 && x < f.W && m_base + 4 * h < f.Cin)
+                                          ? (unsigned)(m_base + 4 * h) * oplane + (unsigned)(y * f.W + x) * 4u : SENT;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) buf_st(ro, base + (unsigned)((r & 3) + 8 * (r >> 2)) * oplane, acc[py][px][n][r]);
+            }
+        }
+    }
+}
+
+template <int DACT>
+int launch_conv5s2_dgrad_d(hipStream_t st, const float *go, const float *yo, const float *w, float *gi, const ConvGeom &f, float dslope) {
+    constexpr int CK = 4;                  // (with the eight accumulator tiles: staging registers for two resident workgroups)
+    const int ub = f.pad >> 1;
+    const int Hu = ((f.H - 1 + f.pad) >> 1) - ub + 1, Wu = ((f.W - 1 + f.pad) >> 1) - ub + 1;
+    const int64_t tiles = (int64_t)f.B * ceil_div(Hu, TY) * ceil_div(Wu, TX);
+    if (tiles > 2147483647LL) return fail(EBFI_ERR_ARG, "conv5x5_backward_data: too many tiles");
+    dim3 grid((unsigned)tiles, (unsigned)ceil_div(f.Cin, 32));
+    {
+        ProfScope ps("conv5s2_dgrad_f32", st, 2.0 * f.B * f.Ho * f.Wo * (double)f.Cout * f.Cin * 25,
+                     4.0 * ((double)f.B * f.Cout * f.Ho * f.Wo * (DACT ? 2 : 1) + (double)f.B * f.Cin * f.H * f.W + (double)f.Cout * f.Cin * 25));
+        hipLaunchKernelGGL((conv5s2_dgrad_f32<CK, DACT>), grid, dim3(256), 0, st, go, yo, w, gi, f, dslope);
+    }
+    return check_launch("conv5s2_dgrad_f32");
+}
+
+// the ebfi_conv5x5_* entry points: stride 1 or 2, 0 <= pad <= 4
+int conv5_geom(ConvGeom &g, const char *who, int B, int Cin, int H, int W, int Cout, int stride, int pad) {
+    if (stride != 1 && stride != 2) return fail(EBFI_ERR_UNSUPPORTED, "%s: stride %d (1 and 2 implemented)", who, stride);
+    if (pad < 0 || pad > 4) return fail(EBFI_ERR_UNSUPPORTED, "%s: padding %d (0 .. 4 implemented)", who, pad);
+    // (a padded map one line short of the window: C's division truncates -1 / 2 to 0, which make_geom would read as one output line)
+    if (H > 0 && W > 0 && (H + 2 * pad < 5 || W + 2 * pad < 5)) return fail(EBFI_ERR_ARG, "%s: empty output", who);
+    return make_geom(g, B, Cin, H, W, Cout, 5, stride, pad, 2);
+}
 }  // namespace
 
 extern "C" int ebfi_pack_table_bf16(const float *src, const int32_t *table, int64_t n, void *out, void *stream) {
@@ -3494,7 +3671,7 @@ extern "C" int ebfi_conv2d_forward(const void *input, const void *weight, const 
     if (dtype != EBFI_F32) return fail(EBFI_ERR_UNSUPPORTED, "conv2d_forward: dtype %d not implemented (fp32 only)", dtype);
     if (act < 0 || act > 2) return fail(EBFI_ERR_ARG, "conv2d_forward: unknown activation %d", act);
     ConvGeom g;
-    if (int rc = make_geom(g, B, Cin, H, W, Cout, ksize, stride, pad, true)) return rc;
+    if (int rc = make_geom(g, B, Cin, H, W, Cout, ksize, stride, pad, 1)) return rc;
     if (B == 0) return EBFI_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float *x = static_cast<const float *>(input), *w = static_cast<const float *>(weight);
@@ -4460,6 +4637,86 @@ extern "C" int ebfi_conv2d_backward_weight_x3g(const void *input, const void *gr
         ProfScope ps("conv_wgrad_reduce_f32", st);
         hipLaunchKernelGGL(conv_wgrad_reduce_f32, dim3((unsigned)ceil_div(n_total, 64)), dim3(256), 0, st, slab, nsplit, n_weight,
                            n_total, static_cast<float *>(grad_weight), static_cast<float *>(grad_bias), 0, ksize * ksize);
+    }
+    return check_launch("conv_wgrad_reduce_f32");
+}
+
+// ------------------------------------------------------------------------------------------------
+// 5x5 convolutions (the recurrent U-Nets at the reference's default kernel size): exact fp32, stride 1 and 2, 0 <= pad <= 4.
+// Entry points of their own: ebfi_conv2d_* keep refusing what they refused before (include/ebfi_hip.h).
+extern "C" int ebfi_conv5x5_forward(const void *input, const void *weight, const void *bias, void *output, int B, int Cin, int H,
+                                    int W, int Cout, int stride, int pad, int act, float slope, void *stream) {
+    if (!input || !weight || !output) return fail(EBFI_ERR_ARG, "conv5x5_forward: null argument");
+    if (act < 0 || act > 2) return fail(EBFI_ERR_ARG, "conv5x5_forward: unknown activation %d", act);
+    ConvGeom g;
+    if (int rc = conv5_geom(g, "conv5x5_forward", B, Cin, H, W, Cout, stride, pad)) return rc;
+    if (B == 0) return EBFI_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const float *x = static_cast<const float *>(input), *w = static_cast<const float *>(weight);
+    const float *bs = static_cast<const float *>(bias);
+    float *o = static_cast<float *>(output);
+    if (stride == 1) return launch_fwd<5, 1, false>(st, x, nullptr, w, bs, o, g, act, slope, 0, 0.f);
+    return launch_fwd<5, 2, false>(st, x, nullptr, w, bs, o, g, act, slope, 0, 0.f);
+}
+
+extern "C" int ebfi_conv5x5_backward_data(const void *grad_output, const void *saved_output, const void *weight, void *grad_input,
+                                          int B, int Cin, int H, int W, int Cout, int stride, int pad, int act, float slope,
+                                          void *stream) {
+    if (!grad_output || !weight || !grad_input) return fail(EBFI_ERR_ARG, "conv5x5_backward_data: null argument");
+    if (act < 0 || act > 2) return fail(EBFI_ERR_ARG, "conv5x5_backward_data: unknown activation %d", act);
+    if (act != ACT_NONE && !saved_output) return fail(EBFI_ERR_ARG, "conv5x5_backward_data: activation needs saved_output");
+    ConvGeom f;   // geometry of the forward conv
+    if (int rc = conv5_geom(f, "conv5x5_backward_data", B, Cin, H, W, Cout, stride, pad)) return rc;
+    if (B == 0) return EBFI_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const float *go = static_cast<const float *>(grad_output), *yo = static_cast<const float *>(saved_output);
+    const float *w = static_cast<const float *>(weight);
+    float *gi = static_cast<float *>(grad_input);
+    if (stride == 1) {   // a forward conv over grad_output with the transposed, flipped filter: channels Cout -> Cin, pad 4 - pad
+        ConvGeom g{B, Cout, f.Ho, f.Wo, Cin, H, W, 4 - pad};
+        return launch_fwd<5, 1, true>(st, go, yo, w, nullptr, gi, g, ACT_NONE, 0.f, act, slope);
+    }
+    if (act == ACT_LEAKY) return launch_conv5s2_dgrad_d<ACT_LEAKY>(st, go, yo, w, gi, f, slope);
+    if (act == ACT_SIGMOID) return launch_conv5s2_dgrad_d<ACT_SIGMOID>(st, go, yo, w, gi, f, slope);
+    return launch_conv5s2_dgrad_d<ACT_NONE>(st, go, nullptr, w, gi, f, 0.f);
+}
+
+extern "C" size_t ebfi_conv5x5_backward_weight_workspace(int B, int Cin, int H, int W, int Cout, int stride, int pad) {
+    ConvGeom g;
+    if (conv5_geom(g, "conv5x5_backward_weight_workspace", B, Cin, H, W, Cout, stride, pad) != EBFI_OK) return 0;
+    return (size_t)wgrad_splits(g, 5, stride) * ((size_t)Cout * Cin * 25 + Cout) * sizeof(float);
+}
+
+extern "C" int ebfi_conv5x5_backward_weight(const void *input, const void *grad_output, const void *saved_output, void *grad_weight,
+                                            void *grad_bias, void *grad_preact_out, int B, int Cin, int H, int W, int Cout, int stride,
+                                            int pad, int act, float slope, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!input || !grad_output || !grad_weight) return fail(EBFI_ERR_ARG, "conv5x5_backward_weight: null argument");
+    if (act < 0 || act > 2) return fail(EBFI_ERR_ARG, "conv5x5_backward_weight: unknown activation %d", act);
+    if (act != ACT_NONE && !saved_output) return fail(EBFI_ERR_ARG, "conv5x5_backward_weight: activation needs saved_output");
+    ConvGeom g;
+    if (int rc = conv5_geom(g, "conv5x5_backward_weight", B, Cin, H, W, Cout, stride, pad)) return rc;
+    const int nsplit = wgrad_splits(g, 5, stride);
+    const int64_t n_weight = (int64_t)Cout * Cin * 25, n_total = n_weight + Cout;
+    const size_t need = (size_t)nsplit * (size_t)n_total * sizeof(float);
+    if (!workspace || workspace_bytes < need)
+        return fail(EBFI_ERR_WORKSPACE, "conv5x5_backward_weight: workspace %zu bytes < required %zu", workspace_bytes, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (B == 0) {
+        (void)hipMemsetAsync(grad_weight, 0, (size_t)n_weight * sizeof(float), st);
+        if (grad_bias) (void)hipMemsetAsync(grad_bias, 0, (size_t)Cout * sizeof(float), st);
+        return EBFI_OK;
+    }
+    const float *x = static_cast<const float *>(input), *go = static_cast<const float *>(grad_output);
+    const float *yo = static_cast<const float *>(saved_output);
+    float *slab = static_cast<float *>(workspace), *gpre = static_cast<float *>(grad_preact_out);
+    const int need_bias = grad_bias != nullptr;
+    const int rc = stride == 1 ? launch_wgrad<5, 1>(st, x, go, yo, slab, gpre, g, act, slope, nsplit, need_bias)
+                               : launch_wgrad<5, 2>(st, x, go, yo, slab, gpre, g, act, slope, nsplit, need_bias);
+    if (rc) return rc;
+    {
+        ProfScope ps("conv_wgrad_reduce_f32", st);
+        hipLaunchKernelGGL(conv_wgrad_reduce_f32, dim3((unsigned)ceil_div(n_total, 64)), dim3(256), 0, st, slab, nsplit, n_weight,
+                           n_total, static_cast<float *>(grad_weight), static_cast<float *>(grad_bias), 0, 25);
     }
     return check_launch("conv_wgrad_reduce_f32");
 }

@@ -4,12 +4,14 @@ The reference's ConvLayer (models/model_misc/submodules.py:159-200) is nn.Conv2d
 activation module; here the forward is one fused kernel (`ebfi_conv2d_forward`), and the backward
 runs the stride-1 data gradient on the same kernel with the activation derivative folded into its
 staging (`ebfi_conv2d_backward_data`) plus a deterministic weight/bias gradient
-(`ebfi_conv2d_backward_weight`).  Configurations the kernels do not cover (kernel sizes other than
-1/3/7, strides other than 1/2, dilation, groups) stay on PyTorch-ROCm's conv; that is a
-GPU library path, never a CPU fallback.  Feature maps of any size >= 2 pixels take the native kernels (partial tiles are
+(`ebfi_conv2d_backward_weight`).  5x5 layers -- the recurrent U-Nets at the reference's default kernel size -- have entry
+points of their own (`ebfi_conv5x5_*`: stride 1 and 2, pad 0..4, exact fp32 in every compute mode; the stride-2 data gradient
+is evaluated per parity class on grad_output itself, with no zero-inserted tensor).  Configurations the kernels do not cover
+(kernel sizes other than 1/3/5/7, strides other than 1/2, a 5x5 layer with pad 5, dilation, groups) stay on PyTorch-ROCm's
+conv; that is a GPU library path, never a CPU fallback.  Feature maps of any size >= 2 pixels take the native kernels (partial tiles are
 masked): MIOpen would otherwise JIT-compile a kernel per small, unusual shape -- minutes on a fresh machine.
 
-Padding: 0 <= pad <= k (`supported`, and make_geom in csrc/conv2d.hip).  The forward and the weight / bias gradient take the
+Padding: 0 <= pad <= k (`supported`, and make_geom in csrc/conv2d.hip); 5x5: 0 <= pad <= 4.  The forward and the weight / bias gradient take the
 whole range; the data-gradient entry points take pad <= k-1 and refuse pad == k.  At pad == k the outer ring of output pixels
 sees padding only, so backward hands them the gradient without that ring at pad = k-1 (`_crop_rings`): a layer that
 `supported` admits runs natively in both directions.
@@ -24,7 +26,8 @@ from . import _native as N
 
 ACT_NONE, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2
 
-# Matrix-core operand precision of the 3x3 / 1x1 stride-1 convs (everything else always runs the exact fp32 kernels):
+# Matrix-core operand precision of the 3x3 / 1x1 stride-1 convs (everything else -- stride 2, wide 7x7, every 5x5 layer -- always
+# runs the exact fp32 kernels):
 #   "fp32"    exact fp32 matrix cores everywhere
 #   "bf16x3"  forward, data and weight gradient with split bf16 operands (hi + lo pairs, three MFMAs per product):
 #             ~1e-5 of fp32, the parity-grade fast mode
@@ -81,14 +84,14 @@ def supported(x, weight, stride, padding, dilation=(1, 1), groups=1):
     when a GPU convolution is actually handed to torch is `left_native`'s business, at the one place that does it."""
     k = weight.shape[-1]
     return bool(x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4 and
-                weight.shape[-2] == k and k in (1, 3, 7) and stride[0] == stride[1] and stride[0] in (1, 2) and
-                not (k == 1 and stride[0] != 1) and padding[0] == padding[1] and 0 <= padding[0] <= k and
+                weight.shape[-2] == k and k in (1, 3, 5, 7) and stride[0] == stride[1] and stride[0] in (1, 2) and
+                not (k == 1 and stride[0] != 1) and padding[0] == padding[1] and 0 <= padding[0] <= (4 if k == 5 else k) and
                 tuple(dilation) == (1, 1) and groups == 1 and x.shape[-1] * x.shape[-2] >= 2)
 
 
 def left_native(x, weight, stride, padding, dilation=(1, 1), groups=1):
-    """Called where a GPU convolution is DISPATCHED to torch (dilation, groups through nn.Conv2d, k outside {1, 3, 7}, stride > 2,
-    non-fp32 / autocast tensors: none occur in the default model) -- i.e. to MIOpen, which compiles a kernel per unusual shape
+    """Called where a GPU convolution is DISPATCHED to torch (dilation, groups through nn.Conv2d, k outside {1, 3, 5, 7}, stride > 2,
+    a 5x5 layer with pad 5, non-fp32 / autocast tensors: none occur in the default model) -- i.e. to MIOpen, which compiles a kernel per unusual shape
     for minutes on a fresh machine.  That must not happen silently: the first time a shape leaves the native path one line goes
     to stderr; with EBFI_STRICT_NATIVE=1 it is an EbfiNativeError instead."""
     if not x.is_cuda:
@@ -137,7 +140,9 @@ class ConvBiasAct(Function):
         lib = N.lib()
         bptr = N.ptr(bias.contiguous() if bias is not None else None)
         with torch.cuda.device_of(x):
-            if _thin_forward(x, weight, bias.contiguous() if bias is not None else None, out, geo, act, slope):
+            if k == 5:                                   # exact fp32 in every compute mode (csrc/conv2d.hip, ebfi_conv5x5_*)
+                rc = lib.ebfi_conv5x5_forward(N.ptr(x), N.ptr(weight), bptr, N.ptr(out), *_geo5(geo), act, slope, N.stream_ptr(x.device))
+            elif _thin_forward(x, weight, bias.contiguous() if bias is not None else None, out, geo, act, slope):
                 rc = 0
             elif _bf16_ok(k, stride) or _x3_ok(k, stride, geo[4]):
                 ws, need = _bf16_ws(lib, geo, x.device)
@@ -166,6 +171,8 @@ class ConvBiasAct(Function):
         gx = gw = gb = None
         need_x = ctx.needs_input_grad[0]
         need_w = ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2])
+        if k == 5:
+            return _backward5(x, weight, y, gout, geo, act, slope, has_bias, need_x, need_w) + (None,) * 5
         bf16 = _bf16_ok(k, stride, mode)
         with torch.cuda.device_of(x):
             st = N.stream_ptr(x.device)
@@ -233,6 +240,36 @@ class ConvBiasAct(Function):
                                                            N.EBFI_F32, st)
                 N.check(rc, "ebfi_conv2d_backward_data")
         return gx, gw, gb, None, None, None, None, None
+
+
+def _geo5(geo):
+    """[B, Cin, H, W, Cout, stride, pad] of a 5x5 layer: the ebfi_conv5x5_* entry points take no kernel size."""
+    return geo[:5] + geo[6:]
+
+
+def _backward5(x, weight, y, gout, geo, act, slope, has_bias, need_x, need_w):
+    """(grad_x, grad_weight, grad_bias) of a 5x5 layer, exact fp32: the slab weight gradient (fixed-order reduction) leaves
+    grad_output * act'(y) for the data gradient when both run; the stride-2 data gradient works on grad_output itself."""
+    lib = N.lib()
+    g5 = _geo5(geo)
+    gx = gw = gb = gpre = None
+    with torch.cuda.device_of(x):
+        st = N.stream_ptr(x.device)
+        if need_w:
+            gw = torch.empty_like(weight)
+            gb = torch.empty(geo[4], dtype=x.dtype, device=x.device) if has_bias else None
+            need = int(lib.ebfi_conv5x5_backward_weight_workspace(*g5))
+            ws = torch.empty(max(need, 4), dtype=torch.uint8, device=x.device)
+            if need_x and act != ACT_NONE:
+                gpre = torch.empty_like(gout)
+            N.check(lib.ebfi_conv5x5_backward_weight(N.ptr(x), N.ptr(gout), N.ptr(y), N.ptr(gw), N.ptr(gb), N.ptr(gpre), *g5, act, slope,
+                                                     N.ptr(ws), need, st), "ebfi_conv5x5_backward_weight")
+        if need_x:
+            gx = torch.empty_like(x)
+            src, sy, a = (gpre, None, ACT_NONE) if gpre is not None else (gout, y, act)
+            N.check(lib.ebfi_conv5x5_backward_data(N.ptr(src), N.ptr(sy), N.ptr(weight), N.ptr(gx), *g5, a,
+                                                   slope if a != ACT_NONE else 0.0, st), "ebfi_conv5x5_backward_data")
+    return gx, gw, gb
 
 
 def _crop_rings(t, ring):

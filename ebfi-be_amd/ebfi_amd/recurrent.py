@@ -2,7 +2,8 @@
 RecurrentConvLayer, ResidualBlock, UpsampleConvLayer and TransposedConvLayer, with the reference's constructor signatures,
 parameter names and state-dict keys.
 
-Where the work runs.  Every convolution goes through ebfi_amd.conv (csrc/conv2d.hip); the cell tails between them and the
+Where the work runs.  Every convolution goes through ebfi_amd.conv (csrc/conv2d.hip: kernel sizes 1, 3, 5 and 7; the 5x5
+layers of RecurrentConvLayer and UpsampleConvLayer at the reference's default kernel size run exact fp32); the cell tails between them and the
 bilinear up-sampling are csrc/recurrent.hip, one launch each and one per backward:
 
   ConvLSTM   cat(x, h) -> Gates (native conv, no activation) -> ebfi_lstm_cell_forward.  Backward recomputes the sigmoids and

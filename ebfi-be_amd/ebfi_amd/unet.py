@@ -4,9 +4,12 @@ reference's `unet_kwargs` dict, keeps the reference's state-dict keys and carrie
 to call (set `net.states = [None] * net.num_encoders` to reset).
 
 Where the work runs: head, encoders, residual blocks, decoders and the prediction layer are ConvLayer / ebfi_amd.recurrent
-modules -- at kernel_size=3, norm=None and use_upsample_conv=True every convolution is a csrc/conv2d.hip kernel, and the cells
-and the up-sampling are csrc/recurrent.hip.  kernel_size=5 has a stride-1 fp32 forward only: its stride-2 encoders and every
-backward are handed to torch and reported through conv.left_native.  The skip additions, the skip concatenations, the crop or
+modules -- at kernel_size in {3, 5} (5 is the reference's default), norm=None and use_upsample_conv=True every convolution is a
+csrc/conv2d.hip kernel, forward and both gradients, and the cells and the up-sampling are csrc/recurrent.hip.  The 5x5 layers
+(head, stride-2 encoders, decoders, SRUNetRecurrent's skip up-samplers) run exact fp32 in every compute mode (ebfi_conv5x5_*);
+their weight gradients are fixed-order slab reductions like the 3x3 ones, so a step stays bit-reproducible.  TransposedConvLayer
+(use_upsample_conv=False) still goes to torch, reported through conv.left_native; with norm in {"BN", "IN"} the layers take
+ConvLayer's non-fused route.  The skip additions, the skip concatenations, the crop or
 pad in front of them and a final torch activation stay torch element-wise ops.  MultiResUNet is not here (it is not recurrent).
 """
 import torch

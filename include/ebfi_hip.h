@@ -330,6 +330,42 @@ int ebfi_conv2d_backward_data_bf16x3(const void *grad_output, const void *saved_
 int ebfi_conv2d_backward_data_s2_bf16x3(const void *grad_preact, const void *weight, void *grad_input, int B, int Cin,
                                         int H, int W, int Cout, int ksize, int pad, void *stream);
 
+/* ------------------------------------------------------------------ 5x5 conv + bias + activation
+ * The recurrent U-Nets of models/model_misc/unet.py at their default kernel_size = 5: head, stride-2 encoders, up-sampling
+ * decoders.  Exact fp32 (v_mfma_f32_32x32x2_f32, fp32 accumulation), contiguous NCHW fp32, no atomics, no allocation and no
+ * synchronisation: capturable.  The ebfi_conv2d_* entry points above refuse exactly what they refused before; 5x5 layers
+ * with gradients come here.
+ *   input [B,Cin,H,W]  weight [Cout,Cin,5,5]  bias [Cout] or NULL  output [B,Cout,Ho,Wo],  Ho = (H + 2*pad - 5)/stride + 1
+ *   stride in {1,2}, 0 <= pad <= 4, any B, Cin, Cout, H, W >= 1 with Ho, Wo >= 1, each sample (plus 64 channels) below 2 GiB.
+ *   act: 0 none, 1 LeakyReLU(slope) (ReLU = slope 0), 2 Sigmoid.
+ * Laws:
+ *   forward        output = act(conv(input, weight) + bias), every element written.
+ *   backward_data  grad_input = conv^T(grad_output * act'(saved_output)), every element written -- the rows / columns that no
+ *                  window reaches when H + 2*pad - 5 is odd at stride 2 as zeros.  saved_output is the forward OUTPUT (act' is
+ *                  taken from it: y > 0 ? 1 : slope, or y (1 - y)); NULL iff act == 0.  Stride 1 is the forward kernel on the
+ *                  transposed, flipped filter with pad 4 - pad; stride 2 is evaluated per parity class of (y + pad, x + pad) on
+ *                  grad_output itself: 3x3, 3x2, 2x3 or 2x2 taps per class, no zero-inserted tensor.
+ *   backward_weight  grad_weight [Cout,Cin,5,5] and (if non-NULL) grad_bias [Cout] of the same product, fully overwritten:
+ *                  one partial slab per workgroup in `workspace`, summed in a fixed order -- bit-reproducible.  Optional side
+ *                  output grad_preact_out [B,Cout,Ho,Wo] = grad_output * act'(saved_output), the very values the kernel
+ *                  multiplies: the caller runs backward_data on it with act = 0.
+ *   ebfi_conv5x5_backward_weight_workspace: bytes backward_weight needs; 0 for a geometry the entry points refuse.
+ * Null pointers, an unknown activation, an activation without saved_output, a non-positive size, an empty output or a
+ * sample beyond the 2 GiB reach -> EBFI_ERR_ARG; stride outside {1,2} or pad outside 0..4 -> EBFI_ERR_UNSUPPORTED; a missing
+ * or short workspace -> EBFI_ERR_WORKSPACE; none touches the GPU.  B == 0 is a no-op, except that backward_weight zero-fills
+ * grad_weight / grad_bias. */
+int ebfi_conv5x5_forward(const void *input, const void *weight, const void *bias, void *output,
+                         int B, int Cin, int H, int W, int Cout, int stride, int pad,
+                         int act, float slope, void *stream);
+int ebfi_conv5x5_backward_data(const void *grad_output, const void *saved_output, const void *weight, void *grad_input,
+                               int B, int Cin, int H, int W, int Cout, int stride, int pad,
+                               int act, float slope, void *stream);
+size_t ebfi_conv5x5_backward_weight_workspace(int B, int Cin, int H, int W, int Cout, int stride, int pad);
+int ebfi_conv5x5_backward_weight(const void *input, const void *grad_output, const void *saved_output,
+                                 void *grad_weight, void *grad_bias, void *grad_preact_out,
+                                 int B, int Cin, int H, int W, int Cout, int stride, int pad,
+                                 int act, float slope, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Weights packed ahead of the call.  ebfi_conv2d_forward_bf16x3 / ebfi_conv2d_backward_data_bf16x3 re-pack `weight` into
  * `workspace` on every call; when `weight` is NULL they take `workspace` as ALREADY holding the packed images
  * ([hi | lo], bf16 [tap][M][K16]: forward M = Cout, K = Cin; data gradient `transposed`: M = Cin, K = Cout, taps flipped;

@@ -8,10 +8,10 @@ per row:
              per call.  `floor_share`: the algorithmic traffic (LSTM forward: 7 C 4 bytes per pixel) at 8 TB/s over the time.
   bilinear   x2 at 8 x 64 x 128 x 128, forward and backward, against F.interpolate and its (atomic) adjoint
   gates      the GRU's update and reset convolutions on the stacked input: two C-output launches against one 2C-output launch
-  step       one UNetFlow step (base 32, 3 encoders, 2 residual blocks, kernel_size 3, sum, convlstm, 8 x 5 x 256 x 256),
-             forward + backward from a fresh state, in both compute modes: milliseconds
+  step       one UNetFlow step (base 32, 3 encoders, 2 residual blocks, kernel_size 3 or --kernel-size, sum, convlstm,
+             8 x 5 x 256 x 256), forward + backward from a fresh state, in both compute modes: milliseconds
 
-usage: python tools/recurrentbench.py [iters] [--no-step]"""
+usage: python tools/recurrentbench.py [iters] [--no-step | --step-only] [--kernel-size K]"""
 import argparse
 import json
 import os
@@ -163,11 +163,11 @@ def bench_gates(B, C, S, iters):
             conv.set_compute_dtype("fp32")
 
 
-def bench_step(iters):
+def bench_step(iters, kernel_size=3):
     from ebfi_amd.unet import UNetFlow
     torch.manual_seed(0)
     net = UNetFlow(dict(base_num_channels=32, num_encoders=3, num_residual_blocks=2, skip_type="sum", norm=None,
-                        use_upsample_conv=True, num_bins=5, recurrent_block_type="convlstm", kernel_size=3)).cuda()
+                        use_upsample_conv=True, num_bins=5, recurrent_block_type="convlstm", kernel_size=kernel_size)).cuda()
     x, cot = rand(8, 5, 256, 256), rand(8, 3, 256, 256)
     params = list(net.parameters())
 
@@ -183,21 +183,25 @@ def bench_step(iters):
             lo, hi = timed(step, iters)
         finally:
             conv.set_compute_dtype("fp32")
-        row(row="step", net="UNetFlow base 32, 3 encoders, 2 residual blocks, k3, sum, convlstm", shape=[8, 5, 256, 256], mode=mode,
+        row(row="step", net="UNetFlow base 32, 3 encoders, 2 residual blocks, k%d, sum, convlstm" % kernel_size, shape=[8, 5, 256, 256], mode=mode,
             ms_per_step=round(lo / 1e3, 3), ms_per_step_max=round(hi / 1e3, 3), parameters=sum(p.numel() for p in params))
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("iters", type=int, nargs="?", default=100)
-    ap.add_argument("--no-step", action="store_true")
+    which = ap.add_mutually_exclusive_group()
+    which.add_argument("--no-step", action="store_true")
+    which.add_argument("--step-only", action="store_true", help="the step rows alone")
+    ap.add_argument("--kernel-size", type=int, default=3, help="kernel_size of the step's UNetFlow (3; 5 is the reference's default)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "recurrentbench needs the MI355X"
-    for S in (64, 128):
-        bench_lstm(8, 64, S, a.iters)
-        bench_gru(8, 64, S, a.iters)
-    bench_bilinear(8, 64, 128, 2, a.iters)
-    for S in (64, 128):
-        bench_gates(8, 64, S, max(a.iters // 4, 10))
+    if not a.step_only:
+        for S in (64, 128):
+            bench_lstm(8, 64, S, a.iters)
+            bench_gru(8, 64, S, a.iters)
+        bench_bilinear(8, 64, 128, 2, a.iters)
+        for S in (64, 128):
+            bench_gates(8, 64, S, max(a.iters // 4, 10))
     if not a.no_step:
-        bench_step(max(a.iters // 10, 5))
+        bench_step(max(a.iters // 10, 5), a.kernel_size)
